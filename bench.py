@@ -17,7 +17,12 @@ CLIP weights every crop would fall below class_sim_thres, so the "" category fil
 demo.py:171 is not applied (the match itself runs).
 Inputs (frames, scene detections) are resident in HBM before the timed region.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+writes what the last timed step's detect call returned and the fusion owner's global boxes after
+it as DIR/<name>.npy (float32).  --full adds everything measured after the timed region: the
+roofline objects (eager re-run, fusion re-run, depth graph replay), the `decode` object of
+--png-depth / --decode and the CPU baseline.
 With --gpus N > 1 and no torch.distributed environment the script starts
 `python -m torch.distributed.run --nproc-per-node N` on itself as a child process (before anything
 touches the GPU) and exits with its status; under torch.distributed.run each rank checks
@@ -74,7 +79,15 @@ def parse(argv=None):
     p.add_argument("--dim", type=int, default=768, help="CuTR ViT width (768 = ViT-B)")
     p.add_argument("--clip-layers", type=int, default=32)
     p.add_argument("--crops", type=int, default=16)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure, after the timed region, the roofline objects (eager re-run of "
+                        "--roofline-steps steps, fusion re-run, depth graph replay), the `decode` "
+                        "object of --png-depth / --decode and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (CuTR predictions, filter mask, CLIP rows, "
+                        "a seeded sample of the back-projected points) and the global boxes after it "
+                        "as DIR/<name>.npy (float32)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--breakdown", action="store_true",
                    help="synchronous fusion, sync between stages, report ms/step of each")
     p.add_argument("--eager", action="store_true", help="no HIP graph for the detect stage")
@@ -129,8 +142,8 @@ def parse(argv=None):
     p.add_argument("--png-depth", action="store_true",
                    help="every frame's depth arrives as a 16-bit PNG file (bytes resident in HBM) and is "
                         "decoded on the GPU inside the timed region (bf_png_decode_depth: cv2.imread "
-                        "IMREAD_UNCHANGED + astype(f32) / depth_scale, capture_stream.py:197-203); the "
-                        "line gains a `decode` object: the GPU PNG and colour-JPEG decode rates with the "
+                        "IMREAD_UNCHANGED + astype(f32) / depth_scale, capture_stream.py:197-203); with "
+                        "--full the line gains a `decode` object: the GPU PNG and colour-JPEG decode rates with the "
                         "host PIL rates beside them")
     p.add_argument("--decode", action="store_true",
                    help="--png-depth, and every keyframe's colour image arrives as a 1296x968 baseline JPEG "
@@ -582,6 +595,35 @@ def host_jpeg_rate(threads, seconds=2.0):
             list(ex.map(dec, range(4 * threads)))
             n += 4 * threads
         return n / (time.perf_counter() - t0), len(blob)
+
+
+def dump_outputs(path, det, fusion, points=1 << 18):
+    """--dump-outputs: what the last timed step left for its caller -- DetectStage.last (the CuTR
+    predictions of every frame, the detection-filter mask, the CLIP rows of the step's crops, and
+    `points` back-projected points drawn with a fixed seed, zero where the depth is invalid) -- and
+    the fusion owner's global boxes after that step, one float32 <name>.npy each"""
+    os.makedirs(path, exist_ok=True)
+    res = det.last["res"]
+    out = {"cutr_" + k.replace("pred_", ""): torch.stack([r.get(k) for r in res])
+           for k, v in res[0].get_fields().items() if torch.is_tensor(v)}
+    out["cutr_boxes_3d"] = torch.stack([r.pred_boxes_3d.tensor for r in res])
+    out["cutr_R"] = torch.stack([r.pred_boxes_3d.R for r in res])
+    out["filter_keep"] = det.last["keep"]
+    _, _, cat_idx, feats, sims = det.last["clip"]
+    out.update(clip_features=feats, clip_sims=sims, clip_class=cat_idx)
+    if det.last.get("xyz") is not None:
+        xyz = torch.stack([x for x, _ in det.last["xyz"]]).reshape(-1, 3)
+        valid = torch.stack([v for _, v in det.last["xyz"]]).reshape(-1).bool()
+        idx = torch.from_numpy(np.random.default_rng(0).integers(0, xyz.shape[0], points)).to(xyz.device)
+        out["xyz_sample"] = torch.where(valid[idx, None], xyz[idx], torch.zeros_like(xyz[idx]))
+        out["xyz_sample_valid"] = valid[idx]
+    out["global_boxes"], out["global_R"] = fusion.boxes()
+    apb = fusion.all_pred_box
+    if apb is not None:
+        out.update({"global_" + k: apb.get(k) for k in ("scores", "features") if apb.has(k)})
+    for k, v in out.items():
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, np.float32)
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def emit(line):
@@ -1046,9 +1088,11 @@ def main(argv=None):
         t = torch.tensor([dt], device="cpu" if rehearse else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, detects[(total_steps - 1) % n_inflight], fusion)
     source = "timed region"
     timed_records = timer      # the non-keyframe depth batches were launched eagerly in the timed region
-    if not any(r[0]["kind"] in ("gemm", "gemm_fp8") for r in timer.records):
+    if args.full and not any(r[0]["kind"] in ("gemm", "gemm_fp8") for r in timer.records):
         # graph mode: time the same kernels launched eagerly on the same inputs, right after the
         # timed region (HIP events on the launch stream, every GEMM / attention launch of the steps)
         detect.use_graph = False
@@ -1063,7 +1107,7 @@ def main(argv=None):
         source = f"eager re-run of {args.roofline_steps} timed steps"
     frames = per_step * args.steps * G
     fus_timer = None
-    if rank == 0:
+    if args.full and rank == 0:
         # the fusion kernels (pairs/s of the 3-D IoU matrix, particle-views/s of the
         # box-fusion fitness) on their own after the timed region: a fresh fusion state machine
         # over the stream's first keyframes, synchronous, HIP events around every launch
@@ -1077,7 +1121,7 @@ def main(argv=None):
             fst.boxes()
         torch.cuda.synchronize()
 
-    if rank == 0:
+    if args.full and rank == 0:
         big = lambda t: t["kind"] == "gemm" and t["large"]
         r_all = roofline_obj(timer.summary(big), "every bf16 linear launch of CLIP ViT-H and CuTR (qkv, "
                              "proj/fc2 + f32 residual, fc1 + GELU): the hand-written k_gemm256q / "
@@ -1162,6 +1206,7 @@ def main(argv=None):
                                    "avg_us": ks["avg_us"], "work_per_launch": ks["flops_per_launch"],
                                    "measured": f"fusion re-run over {args.roofline_keyframes} keyframes"}
         r_all["measured"] = source
+    if rank == 0:
         line = base_line(args, N, frames, dt, per_step * G, n_inflight)
         if B0 < B:
             line["config"]["rank0_batch"] = B0
@@ -1194,7 +1239,7 @@ def main(argv=None):
             line["fusion_owner"] = {"busy_ms_per_step": 1e3 * owner[0] / args.steps,
                                     "keyframes": owner[1],
                                     "ms_per_keyframe": 1e3 * owner[0] / owner[1]}
-        if args.clip_fp8:
+        if args.full and args.clip_fp8:
             f8 = roofline_obj(timer.summary(lambda t: t["kind"] == "gemm_fp8"),
                               "k_gemm256p<*, *, fp8> (CLIP qkv, fc1 + GELU -> fp8, fc2 + f32 residual; "
                               "block-scaled fp8 MFMA)", "mfma", pmc_key=PMC_KEYS["fp8_gemm"],
@@ -1204,14 +1249,25 @@ def main(argv=None):
         # the headline is the figure north_star names: "fraction of the ViT-attention MFMA
         # roofline" (every CLIP + CuTR attention launch); the GEMM family -- most of the GPU time --
         # is roofline_components.gemm
-        comps["gemm"] = r_all
-        head = dict(comps["attention"])
-        head["note"] = ("north_star's ViT-attention MFMA roofline: algorithmic 4*Sq*Sk*D FLOPs of every "
-                        "CLIP ViT-H/14 and CuTR attention launch / their HIP-event time / the 2.5 PF dense "
-                        "bf16 peak; the GEMM family is roofline_components.gemm")
-        line["roofline"] = head
-        line["roofline_components"] = comps
+        if args.full:
+            comps["gemm"] = r_all
+            head = dict(comps["attention"])
+            head["note"] = ("north_star's ViT-attention MFMA roofline: algorithmic 4*Sq*Sk*D FLOPs of every "
+                            "CLIP ViT-H/14 and CuTR attention launch / their HIP-event time / the 2.5 PF dense "
+                            "bf16 peak; the GEMM family is roofline_components.gemm")
+            line["roofline"] = head
+            line["roofline_components"] = comps
         if png_in is not None:
+            line["config"]["depth_input"] = ("16-bit PNG bytes in HBM, decoded on the GPU in the timed region" +
+                                             (f" (one group of {args.jpeg_ahead} steps ahead on a decode stream)"
+                                              if args.decode else " (in the step's stream)"))
+            if jpg_in is not None:
+                line["config"]["color_input"] = (f"1296x968 baseline JPEG bytes in HBM (q90 4:2:0, "
+                                                 f"{jpg_in['bytes_per_frame'] / 1e3:.0f} KB), decoded on the GPU "
+                                                 f"one group of {jpg_in['D']} steps ahead on a decode stream "
+                                                 f"(bf_jpeg_decode_rgb + bf_cv2_resize_u8 to {FW}x{FH}) inside the "
+                                                 f"timed region")
+        if args.full and png_in is not None:
             # the GPU decode alone: one step's files (keyframes + non-keyframes), HIP events, after
             # the timed region; and PIL on 16 host threads over the same files
             files, offs, offs_h = png_in["steps"][args.warmup]
@@ -1247,21 +1303,13 @@ def main(argv=None):
                                   jpeg_kernel="bf_jpeg_decode_rgb (k_jpeg_parse + k_jpeg_entropy + k_jpeg_idct "
                                               "+ k_jpeg_color), bit-exact to libjpeg's defaults",
                                   keyframes_per_s_needed=line["value"] / G)
-            line["config"]["depth_input"] = ("16-bit PNG bytes in HBM, decoded on the GPU in the timed region" +
-                                             (f" (one group of {args.jpeg_ahead} steps ahead on a decode stream)"
-                                              if args.decode else " (in the step's stream)"))
             if jpg_in is not None:
                 spans = [a.elapsed_time(b) for a, b in jpg_in["spans"][1:]]
                 line["decode"]["gpu_jpeg_group_ms"] = {"files": jpg_in["D"] * Bm, "mean": float(np.mean(spans)),
                                                       "max": float(np.max(spans))} if spans else None
-                line["config"]["color_input"] = (f"1296x968 baseline JPEG bytes in HBM (q90 4:2:0, "
-                                                 f"{jpg_in['bytes_per_frame'] / 1e3:.0f} KB), decoded on the GPU "
-                                                 f"one group of {jpg_in['D']} steps ahead on a decode stream "
-                                                 f"(bf_jpeg_decode_rgb + bf_cv2_resize_u8 to {FW}x{FH}) inside the "
-                                                 f"timed region")
         if args.breakdown:
             line["breakdown_ms_per_step"] = {k: 1e3 * v / args.steps for k, v in brk.items()}
-        if not args.no_cpu_baseline and N == 1:   # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and N == 1:   # rank 0 at N=1 only
             line["cpu_baseline"] = (cpu_baseline(cutr, clip_vis, args, scene) if args.cpu_detect_frames > 0 else None)
         emit(line)
     if dist is not None:

@@ -7,43 +7,44 @@
 #   profiles/<r>_pmc.json       HBM-side bytes per launch (2 x FETCH_SIZE + WRITE_SIZE, separate
 #                               --pmc passes) per kernel name and for the bench line's roofline
 #                               kernels; SQ instruction mix of the attention kernels
-#   profiles/<r>_bench_default.json                            a plain bench run
+#   profiles/<r>_bench_default.json                            a default bench run with --full
 # usage: scripts/profile_round.sh r02 [all|pmc|trace]
 set -o pipefail
 R=${1:-r02}
 ONLY=${2:-all}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out/prof_$R gpurun_out/profiles
-P=gpurun_out/profiles     # copied into profiles/ afterwards (only gpurun_out/ comes back from the box)
+OUT=${BF_PROF_OUT:-prof_out}     # logs and the regenerated profiles go here
+mkdir -p $OUT/prof_$R $OUT/profiles
+P=$OUT/profiles     # copied into profiles/ afterwards
 
 if [ "$ONLY" = all ] || [ "$ONLY" = trace ]; then
 echo "== kernel trace"
 rm -rf /tmp/kt_$R
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$R -o run -- \
-    python3 -u bench.py --no-cpu-baseline --steps 40 > gpurun_out/prof_$R/kt.log 2>&1 || { tail -20 gpurun_out/prof_$R/kt.log; exit 1; }
+    python3 -u bench.py --full --no-cpu-baseline --steps 40 > $OUT/prof_$R/kt.log 2>&1 || { tail -20 $OUT/prof_$R/kt.log; exit 1; }
 cp "$(find /tmp/kt_$R -name '*kernel_stats.csv' | head -1)" $P/${R}_bench_kernel_stats.csv
 cp "$(find /tmp/kt_$R -name '*domain_stats.csv' | head -1)" $P/${R}_bench_domain_stats.csv
-grep '"metric"' gpurun_out/prof_$R/kt.log > $P/${R}_bench_under_rocprof.json
+grep '"metric"' $OUT/prof_$R/kt.log > $P/${R}_bench_under_rocprof.json
 echo "== roofline kernel trace (eager, one detect stream: every launch the bench's HIP-event timer sees)"
 rm -rf /tmp/rk_$R
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rk_$R -o run -- \
-    python3 -u bench.py --eager --inflight 1 --steps 10 --warmup 1 --no-cpu-baseline > gpurun_out/prof_$R/rk.log 2>&1 || { tail -20 gpurun_out/prof_$R/rk.log; exit 1; }
+    python3 -u bench.py --full --eager --inflight 1 --steps 10 --warmup 1 --no-cpu-baseline > $OUT/prof_$R/rk.log 2>&1 || { tail -20 $OUT/prof_$R/rk.log; exit 1; }
 cp "$(find /tmp/rk_$R -name '*kernel_stats.csv' | head -1)" $P/${R}_roofline_kernel_stats.csv
-grep '"metric"' gpurun_out/prof_$R/rk.log > $P/${R}_roofline_bench.json
+grep '"metric"' $OUT/prof_$R/rk.log > $P/${R}_roofline_bench.json
 fi
 
 if [ "$ONLY" = all ] || [ "$ONLY" = pmc ]; then
 # PMC_EXTRA: extra bench flags for a workload's own PMC file (e.g. R=r02_fp8 PMC_EXTRA="--clip-fp8 --vocab 200")
-PMC_CMD="python3 -u bench.py --steps 2 --warmup 1 --eager --inflight 1 --no-cpu-baseline --roofline-steps 1 ${PMC_EXTRA:-}"
+PMC_CMD="python3 -u bench.py --full --steps 2 --warmup 1 --eager --inflight 1 --no-cpu-baseline --roofline-steps 1 ${PMC_EXTRA:-}"
 # SQ_PASS: an extra pass of SQ counters (names as `rocprofv3 -L` lists them on the box)
 for pass in FETCH_SIZE WRITE_SIZE ${SQ_PASS:+"$SQ_PASS"}; do
   tag=$(echo $pass | cut -d' ' -f1)
   echo "== pmc $pass"
   rm -rf /tmp/pmc_${R}_$tag
   timeout -s KILL 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d /tmp/pmc_${R}_$tag -o p -- \
-      $PMC_CMD > gpurun_out/prof_$R/pmc_$tag.log 2>&1 || { tail -20 gpurun_out/prof_$R/pmc_$tag.log; exit 1; }
+      $PMC_CMD > $OUT/prof_$R/pmc_$tag.log 2>&1 || { tail -20 $OUT/prof_$R/pmc_$tag.log; exit 1; }
 done
-python3 - "$R" <<'PY'
+python3 - "$R" "$P" <<'PY'
 import csv, glob, json, re, sys, collections
 R = sys.argv[1]
 per = collections.defaultdict(lambda: collections.defaultdict(lambda: collections.defaultdict(float)))
@@ -89,7 +90,7 @@ for key, pats in groups.items():
     w = sum(k["FETCH_SIZE_dispatches"] for _, k in sel)
     out[key] = {"bytes_per_launch": sum(k["bytes_per_launch"] * k["FETCH_SIZE_dispatches"] for _, k in sel) / w,
                 "dispatches": w, "kernel_names": [n for n, _ in sel]}
-json.dump(out, open(f"gpurun_out/profiles/{R}_pmc.json", "w"), indent=1)
+json.dump(out, open(f"{sys.argv[2]}/{R}_pmc.json", "w"), indent=1)
 print(json.dumps({k: v for k, v in out.items() if k != "kernels"}, indent=1))
 PY
 [ $? -eq 0 ] || exit 1
@@ -97,7 +98,7 @@ fi
 
 if [ "$ONLY" = all ]; then
 echo "== bench default"
-timeout -k 10 400 python3 -u bench.py > gpurun_out/prof_$R/default.log 2>&1 || { tail -20 gpurun_out/prof_$R/default.log; exit 1; }
-grep '"metric"' gpurun_out/prof_$R/default.log > $P/${R}_bench_default.json
+timeout -k 10 400 python3 -u bench.py --full > $OUT/prof_$R/default.log 2>&1 || { tail -20 $OUT/prof_$R/default.log; exit 1; }
+grep '"metric"' $OUT/prof_$R/default.log > $P/${R}_bench_default.json
 cat $P/${R}_bench_default.json
 fi

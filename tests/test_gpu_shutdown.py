@@ -57,7 +57,7 @@ def test_exit_with_running_fusion_worker():
 def test_bench_sim_ranks_exits_cleanly():
     """bench.py's own exit path: detect graphs on masked streams, the fusion worker fusing two
     ranks' keyframes through the native sequencer, CPU-side results, then a normal exit"""
-    r = _run([sys.executable, "-u", "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = _run([sys.executable, "-u", "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
               "--sim-ranks", "2", "--fusion-cus", "32", "--mask-cus", "1", "--dim", "192",
               "--clip-layers", "2", "--crops", "2", "--roofline-steps", "1", "--roofline-keyframes", "4"], 115)
     assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
