@@ -867,6 +867,53 @@ def png_workspace_bytes(F, H, W, total_file_bytes):
     return int(L.bf_png_workspace_bytes(F, H, W, total_file_bytes))
 
 
+def png_decode_rgb(files, offsets, H, W, out=None, offsets_host=None, check=True, work=None):
+    """cv2.imread(color_path) + cvtColor(BGR2RGB) for F 8-bit PNGs (CA-1M's rgb/*.png,
+    capture_stream.py:402): grey, RGB, grey + alpha or RGBA, non-interlaced (transparency is dropped,
+    not composited, as cv2's default flag does); files / offsets / offsets_host as png_decode_u16
+    -> out u8 [F,H,W,3] in RGB order and the int32 status word per file (BF_PNG_* bits).  A batch may
+    mix the four kinds.  check=True synchronises and raises on any file that did not decode."""
+    _need(files, torch.uint8, "files")
+    _need(offsets, torch.int64, "offsets")
+    if offsets_host is None:
+        offsets_host = offsets.cpu()
+    oh = [int(v) for v in offsets_host]
+    F_ = len(oh) - 1
+    if F_ < 0 or offsets.numel() != F_ + 1:
+        raise HipError("png_decode_rgb: offsets [F+1]")
+    total = oh[-1]
+    if total > files.numel():
+        raise HipError("png_decode_rgb: offsets run past the file bytes")
+    mx = max((oh[i + 1] - oh[i] for i in range(F_)), default=0)
+    wb = png_rgb_workspace_bytes(F_, H, W, total)
+    if work is None or work.numel() < wb:
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=files.device)
+    if out is None:
+        out = torch.empty((F_, H, W, 3), dtype=torch.uint8, device=files.device)
+    _need(out, torch.uint8, "out")
+    if out.numel() != F_ * H * W * 3:
+        raise HipError("png_decode_rgb: out [F,H,W,3]")
+    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=files.device)
+    _check(lib().bf_png_decode_rgb(_ptr(files), _ptr(offsets), c_int(F_), c_int(H), c_int(W), ctypes.c_longlong(total),
+                                   ctypes.c_longlong(mx), _ptr(out), _ptr(work), c_size_t(wb), _ptr(status),
+                                   _stream()), "bf_png_decode_rgb")
+    if check and F_:
+        st = status[:F_].cpu()
+        bad = torch.nonzero(st).flatten().tolist()
+        if bad:
+            f = bad[0]
+            why = ", ".join(v for k, v in PNG_STATUS.items() if int(st[f]) & k)
+            raise HipError(f"png_decode_rgb: {len(bad)} of {F_} files did not decode (file {f}: {why})")
+    return out, status[:F_]
+
+
+def png_rgb_workspace_bytes(F, H, W, total_file_bytes):
+    L = lib()
+    L.bf_png_rgb_workspace_bytes.restype = c_size_t
+    L.bf_png_rgb_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.c_longlong]
+    return int(L.bf_png_rgb_workspace_bytes(F, H, W, total_file_bytes))
+
+
 JPEG_STATUS = {1: "bad / missing marker segment", 2: "unsupported JPEG kind (not baseline 1/3-component h2v2/h2v1/h1v1)",
                4: "size mismatch", 8: "corrupt entropy-coded data"}
 

@@ -8,8 +8,8 @@ camera -> world pose), the frame rotated to the upright orientation first (torch
 whatever device the frame is on).  `make_sample_decoded` / `DecodedFrameStream` take decoded
 colour + 16-bit depth frames and run the rest of the streams' per-frame work on the GPU
 (bf_ingest_rgbd: cvtColor, cv2.resize, depth scaling, rotation); the 16-bit depth PNGs
-(bf_png_decode_u16) and the baseline colour JPEGs (bf_jpeg_decode_rgb) are decoded on the GPU too,
-or on host threads (PIL) when configured so.
+(bf_png_decode_u16), the baseline colour JPEGs (bf_jpeg_decode_rgb) and the 8-bit colour PNGs of
+CA-1M (bf_png_decode_rgb) are decoded on the GPU too, or on host threads (PIL) when configured so.
 """
 from __future__ import annotations
 
@@ -139,6 +139,26 @@ def decode_color_jpegs(blobs, H, W, device="cuda"):
     return out
 
 
+def decode_color_pngs(blobs, H, W, device="cuda"):
+    """cv2.imread(color_path) + cvtColor(BGR2RGB) (capture_stream.py:402, CA-1M's rgb/*.png) for a
+    batch of 8-bit PNG files (their bytes: grey, RGB, with or without alpha), decoded on the GPU
+    (bf_png_decode_rgb) -> u8 [F, H, W, 3] RGB on device; raises if any file does not decode"""
+    from boxfusion_amd import _lib
+    files, offs, offs_h = upload_files(blobs, device)
+    out, _ = _lib.png_decode_rgb(files, offs, H, W, offsets_host=offs_h)
+    return out
+
+
+PNG_SIG = b"\x89PNG\r\n\x1a\n"
+
+
+def png_size(blob):
+    """(W, H) from a PNG's IHDR (the file's first 24 bytes); ValueError if it is no PNG"""
+    if blob[:8] != PNG_SIG or blob[12:16] != b"IHDR" or len(blob) < 24:
+        raise ValueError("not a PNG")
+    return int.from_bytes(blob[16:20], "big"), int.from_bytes(blob[20:24], "big")
+
+
 def jpeg_size(blob):
     """(W, H) from a JPEG's SOFn frame header (file bytes); ValueError if there is none"""
     if blob[:2] != b"\xff\xd8":
@@ -162,16 +182,18 @@ class DecodedFrameStream:
     """a ScanNet / CA-1M style frame directory as demo.py's dataset: colour JPEG / PNG and 16-bit
     depth PNG paths plus camera -> world poses.  Depth PNGs are decoded on the GPU
     (bf_png_decode_u16, `batch` files per launch) or on host threads; colour images on the host
-    (PIL: cv2 is absent here) or, baseline JPEGs, on the GPU (bf_jpeg_decode_rgb).  Everything
-    after decode runs in bf_ingest_rgbd on `device`."""
+    (PIL: cv2 is absent here) or, baseline JPEGs and 8-bit PNGs, on the GPU (bf_jpeg_decode_rgb,
+    bf_png_decode_rgb).  Everything after decode runs in bf_ingest_rgbd on `device`."""
 
     def __init__(self, color_paths, depth_paths, poses, K, depth_scale, device="cuda", video_id=0, batch=16,
                  depth_decode="gpu", host_threads=16, color_decode="host"):
         """depth_decode "gpu": bf_png_decode_u16 on `batch` files per launch; "host": PIL on
         `host_threads` threads (the faster choice when a GPU's share of host cores decodes more
         files per second than the GPU path, DESIGN.md §4 "Depth PNG decode").  color_decode "gpu":
-        bf_jpeg_decode_rgb on `batch` baseline JPEGs per launch (a file of another kind raises);
-        "host": PIL, one file at a time"""
+        each file's magic bytes choose its decoder, the batch's baseline JPEGs go through
+        bf_jpeg_decode_rgb and its 8-bit PNGs through bf_png_decode_rgb, one launch each (a file that
+        is neither raises ValueError, one its decoder refuses HipError); "host": PIL, one file at a
+        time"""
         if not (len(color_paths) == len(depth_paths) == len(poses)):
             raise ValueError("one colour image, depth map and pose per frame")
         if depth_decode not in ("gpu", "host"):
@@ -190,9 +212,37 @@ class DecodedFrameStream:
     def _depth_size(self, path):
         with open(path, "rb") as fh:
             head = fh.read(24)
-        if head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
-            raise ValueError(f"{path}: not a PNG")
-        return int.from_bytes(head[20:24], "big"), int.from_bytes(head[16:20], "big")
+        try:
+            W, H = png_size(head)
+        except ValueError:
+            raise ValueError(f"{path}: not a PNG") from None
+        return H, W
+
+    def _decode_colors(self, idx):
+        """the batch's colour files on the GPU -> one u8 [H, W, 3] RGB tensor per frame, in frame order"""
+        blobs, kinds = [], []
+        for i in idx:
+            with open(self.color[i], "rb") as fh:
+                blobs.append(fh.read())
+            if blobs[-1][:8] == PNG_SIG:
+                kinds.append("png")
+            elif blobs[-1][:2] == b"\xff\xd8":
+                kinds.append("jpeg")
+            else:
+                raise ValueError(f"{self.color[i]}: neither a PNG nor a JPEG")
+        cols = [None] * len(blobs)
+        for kind, size, decode in (("png", png_size, decode_color_pngs), ("jpeg", jpeg_size, decode_color_jpegs)):
+            sel = [j for j, k in enumerate(kinds) if k == kind]
+            if not sel:
+                continue
+            try:
+                Wc, Hc = size(blobs[sel[0]])
+            except ValueError as e:
+                raise ValueError(f"{self.color[idx[sel[0]]]}: {e}") from None
+            out = decode([blobs[j] for j in sel], Hc, Wc, self.dev)
+            for n, j in enumerate(sel):
+                cols[j] = out[n]
+        return cols
 
     def __iter__(self):
         from PIL import Image
@@ -212,12 +262,7 @@ class DecodedFrameStream:
                 deps = torch.from_numpy(np.stack(arrs).view(np.int16)).to(self.dev).view(torch.uint16)
             cols = None
             if self.color_decode == "gpu":
-                blobs = []
-                for i in idx:
-                    with open(self.color[i], "rb") as fh:
-                        blobs.append(fh.read())
-                Wc, Hc = jpeg_size(blobs[0])
-                cols = decode_color_jpegs(blobs, Hc, Wc, self.dev)
+                cols = self._decode_colors(idx)
             for j, i in enumerate(idx):
                 if cols is not None:
                     rgb_t = cols[j]

@@ -1,8 +1,10 @@
-// bf_png.hip — 16-bit depth PNG decode on the GPU (the decode half of frame
-// ingestion): cv2.imread(depth_path, cv2.IMREAD_UNCHANGED) of the reference's capture streams
-// (capture_stream.py:197 ScanNet, :405 CA-1M) for the files those datasets ship — greyscale,
-// 16 bits per sample, not interlaced.  PNG is lossless, so the result is defined bit for bit by
-// the file (RFC 1950 zlib / RFC 1951 deflate / PNG 1.2 filtering); any other image kind is
+// bf_png.hip — PNG decode on the GPU (the decode half of frame ingestion):
+// cv2.imread(depth_path, cv2.IMREAD_UNCHANGED) of the reference's capture streams
+// (capture_stream.py:197 ScanNet, :405 CA-1M) for the depth files those datasets ship — greyscale,
+// 16 bits per sample, not interlaced (bf_png_decode_u16 / _depth) — and cv2.imread(color_path) +
+// cvtColor(BGR2RGB) for CA-1M's rgb/*.png (:402) — 8 bits per sample, grey / RGB with or without
+// alpha, not interlaced (bf_png_decode_rgb).  PNG is lossless, so the result is defined bit for bit
+// by the file (RFC 1950 zlib / RFC 1951 deflate / PNG 1.2 filtering); any other image kind is
 // reported, not decoded.
 //
 // Four launches per batch of F files (device bytes of the files back to back + F+1 offsets):
@@ -16,6 +18,8 @@
 //   k_png_unfilter one wave per file undoes the per-row filters (None / Sub / Up / Average /
 //                  Paeth on 2-byte pixels) on a diagonal wavefront: lane l holds row b0 + l and
 //                  runs one pixel behind lane l - 1, so the row above arrives by a lane shift
+//                  (k_png_unfilter_rgb8: the same wavefront on 8-bit pixels of 1 to 4 bytes, one
+//                  pixel packed in a register, written as RGB)
 // Status per file (int32, BF_PNG_* bits) says what was wrong with a file that did not decode.
 #include "bf_common.h"
 
@@ -27,8 +31,10 @@
 #endif
 
 struct PngSegTable {              // per file, in the workspace
-    uint32_t nseg, zlen, width, height;
+    uint32_t nseg, zlen;
+    uint32_t bpp, row_bytes;      // bytes per pixel; filtered row = 1 filter byte + bpp x W
 };
+enum { PNG_GREY16 = 0, PNG_COLOUR8 = 1 };      // the image kinds an entry point's parse accepts
 struct PngSeg {                   // one IDAT chunk: logical start in the zlib stream, byte offset in the file
     uint32_t zstart, phys;
 };
@@ -38,14 +44,15 @@ __host__ __device__ inline long long png_seg0(long long file_off, int f) { retur
 
 static inline size_t png_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// workspace: [F seg tables][IDAT lists][zlib streams: file f at zoff(f)][filtered rows F x H x (2W+1)]
+// workspace: [F seg tables][IDAT lists][zlib streams: file f at zoff(f)][filtered rows F x H x row bytes]
 static inline size_t png_tab_bytes(int F) { return png_align((size_t)F * sizeof(PngSegTable), 256); }
 static inline size_t png_list_bytes(int F, long long total) {
     return png_align(((size_t)total / 12 + (size_t)F + 1) * sizeof(PngSeg), 256);
 }
 static inline size_t png_z_bytes(int F, long long total) { return png_align((size_t)total + 32 * (size_t)F + 64, 256); }
-// filtered rows of one file: H x (2W + 1) bytes, each file's block 16-B aligned
-__host__ __device__ inline uint64_t png_rstride(int H, int W) { return ((uint64_t)H * (2 * (uint64_t)W + 1) + 15) & ~15ull; }
+// filtered rows of one file: H x (bpp W + 1) bytes at the widest bpp the entry point accepts (2 for
+// the 16-bit grey decode, 4 for the colour decode), each file's block 16-B aligned
+static inline uint64_t png_rstride(int H, int W, int bpp) { return ((uint64_t)H * ((uint64_t)bpp * W + 1) + 15) & ~15ull; }
 __host__ __device__ inline long long png_zoff(long long file_off, int f) { return ((file_off + 15) & ~15ll) + 32ll * f; }
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -66,6 +73,9 @@ __device__ __forceinline__ uint32_t ld_be32(const uint8_t* p) {
 }
 
 // ---- chunk walk ----------------------------------------------------------------------------
+// kKind: what the entry point decodes -- PNG_GREY16 (16-bit grey), PNG_COLOUR8 (8-bit grey, RGB,
+// grey + alpha, RGBA); any other IHDR is BF_PNG_UNSUPPORTED
+template <int kKind>
 __global__ void __launch_bounds__(64) k_png_parse(const uint8_t* __restrict__ files, const int64_t* __restrict__ offs,
                                                   int F, int H, int W, PngSegTable* __restrict__ tabs,
                                                   PngSeg* __restrict__ segs, int32_t* __restrict__ status) {
@@ -77,7 +87,7 @@ __global__ void __launch_bounds__(64) k_png_parse(const uint8_t* __restrict__ fi
     PngSegTable* T = tabs + f;
     PngSeg* S = segs + png_seg0(base, f);
     int st = 0;
-    uint32_t nseg = 0, zlen = 0;
+    uint32_t nseg = 0, zlen = 0, bpp = 2;
     const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
     if (n < 8 + 25 + 12) st |= BF_PNG_BAD_SIGNATURE;
     for (int i = 0; i < 8 && !st; ++i)
@@ -94,7 +104,14 @@ __global__ void __launch_bounds__(64) k_png_parse(const uint8_t* __restrict__ fi
                 if (type != 0x49484452u || len != 13) { st |= BF_PNG_BAD_HEADER; break; }   // IHDR first
                 const uint32_t w = ld_be32(d), h = ld_be32(d + 4);
                 if (w == 0 || h == 0 || d[10] != 0 || d[11] != 0) { st |= BF_PNG_BAD_HEADER; break; }
-                if (d[8] != 16 || d[9] != 0 || d[12] != 0) st |= BF_PNG_UNSUPPORTED;      // 16-bit grey only
+                if constexpr (kKind == PNG_GREY16) {
+                    if (d[8] != 16 || d[9] != 0 || d[12] != 0) st |= BF_PNG_UNSUPPORTED;      // 16-bit grey only
+                } else {
+                    // 8-bit grey (type 0), RGB (2), grey + alpha (4), RGBA (6): 1 + 2 (colour) + 1 (alpha) bytes
+                    const uint32_t ct = d[9];
+                    if (d[8] != 8 || (ct & ~6u) || d[12] != 0) st |= BF_PNG_UNSUPPORTED;
+                    bpp = 1 + (ct & 2u) + ((ct >> 2) & 1u);
+                }
                 if ((int)w != W || (int)h != H) st |= BF_PNG_SIZE;
                 seen_ihdr = true;
             } else if (type == 0x49444154u) {            // IDAT
@@ -117,8 +134,8 @@ __global__ void __launch_bounds__(64) k_png_parse(const uint8_t* __restrict__ fi
     if (threadIdx.x == 0) {
         T->nseg = st ? 0 : nseg;
         T->zlen = st ? 0 : zlen;
-        T->width = W;
-        T->height = H;
+        T->bpp = bpp;
+        T->row_bytes = bpp * (uint32_t)W + 1u;
         status[f] = st;
     }
 }
@@ -443,7 +460,7 @@ __device__ __noinline__ PngTok png_serial_token(PngLds* L, const uint32_t* z, ui
 }
 
 __global__ void __launch_bounds__(64) k_png_inflate(const uint8_t* __restrict__ zbase, const int64_t* __restrict__ offs,
-                                                    const PngSegTable* __restrict__ tabs, int H, int W,
+                                                    const PngSegTable* __restrict__ tabs, int H, uint64_t fstride,
                                                     uint8_t* __restrict__ rows, int32_t* __restrict__ status) {
     __shared__ PngLds L;
     const int f = blockIdx.x;
@@ -451,8 +468,8 @@ __global__ void __launch_bounds__(64) k_png_inflate(const uint8_t* __restrict__ 
     if (status[f]) return;
     const PngSegTable* T = tabs + f;
     const uint32_t zlen = T->zlen;
-    const uint32_t total = (uint32_t)H * (2u * (uint32_t)W + 1u);      // < 2^31 (host check)
-    uint8_t* out = rows + (uint64_t)f * png_rstride(H, W);
+    const uint32_t total = (uint32_t)H * T->row_bytes;                  // < 2^31 (host check)
+    uint8_t* out = rows + (uint64_t)f * fstride;
     const uint32_t* z = reinterpret_cast<const uint32_t*>(zbase + png_zoff(offs[f], f));
     const uint32_t lim = (zlen + 15) / 4;                                // the 16 zero bytes after the stream
     int st = 0;
@@ -718,8 +735,9 @@ __device__ __forceinline__ uint32_t png_pred(uint32_t ft, uint32_t a, uint32_t b
 // OutT uint16_t: the samples (cv2.imread IMREAD_UNCHANGED); float: sample / depth_scale in IEEE
 // f32 division (capture_stream.py:203, depth_data.astype(np.float32) / self.depth_scale)
 template <typename OutT>
-__global__ void __launch_bounds__(64) k_png_unfilter(const uint8_t* __restrict__ rows, int H, int W, float depth_scale,
-                                                     OutT* __restrict__ out, int32_t* __restrict__ status) {
+__global__ void __launch_bounds__(64) k_png_unfilter(const uint8_t* __restrict__ rows, int H, int W, uint64_t fstride,
+                                                     float depth_scale, OutT* __restrict__ out,
+                                                     int32_t* __restrict__ status) {
     __shared__ uint16_t prev[4096];      // the last row of the previous band (lane 63's outputs)
     const int f = blockIdx.x;
     const int lane = threadIdx.x;
@@ -728,7 +746,7 @@ __global__ void __launch_bounds__(64) k_png_unfilter(const uint8_t* __restrict__
 #ifdef PNG_STATS
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    const uint8_t* src = rows + (uint64_t)f * png_rstride(H, W);
+    const uint8_t* src = rows + (uint64_t)f * fstride;
     OutT* dst = out + (uint64_t)f * H * W;
     int bad = 0;
     for (int b0 = 0; b0 < H; b0 += 64) {
@@ -810,34 +828,178 @@ __global__ void __launch_bounds__(64) k_png_unfilter(const uint8_t* __restrict__
 #endif
 }
 
-BF_API size_t bf_png_workspace_bytes(int F, int H, int W, long long total_file_bytes) {
+// ---- unfilter, 8-bit samples (bpp = 1 .. 4) -> RGB -------------------------------------------
+struct __attribute__((packed)) PngU32 { uint32_t v; };          // a dword at any byte address
+struct __attribute__((packed)) PngU96 { uint32_t a, b, c; };    // four RGB pixels at any byte address
+
+// The wavefront of k_png_unfilter on pixels of the file's bpp bytes: one pixel is one register
+// (byte k = sample k of the pixel, the bytes past bpp zero), the predictor runs per byte against the
+// byte bpp to the left, i.e. the same byte of the previous pixel.  The RGB pixels (grey replicated,
+// alpha dropped) leave through a 96-bit shift register, 12 bytes per store every fourth pixel.
+__global__ void __launch_bounds__(64) k_png_unfilter_rgb8(const uint8_t* __restrict__ rows,
+                                                          const PngSegTable* __restrict__ tabs, int H, int W,
+                                                          uint64_t fstride, uint8_t* __restrict__ out,
+                                                          int32_t* __restrict__ status) {
+    __shared__ uint32_t prev[4096];      // the last row of the previous band (lane 63's pixels)
+    const int f = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (status[f]) return;
+    const uint32_t bpp = rfl(tabs[f].bpp);
+    const uint64_t S = (uint64_t)bpp * W + 1;
+    const uint32_t keep = bpp >= 4 ? 0xffffffffu : (1u << (8 * bpp)) - 1u;
+    const bool grey = bpp < 3;
+    const uint8_t* src = rows + (uint64_t)f * fstride;
+    uint8_t* dst = out + (uint64_t)f * H * W * 3;
+    int bad = 0;
+    for (int b0 = 0; b0 < H; b0 += 64) {
+        const int r = b0 + lane;
+        const bool valid = r < H;
+        const uint8_t* row = src + (uint64_t)(valid ? r : 0) * S;
+        const uint32_t ft = valid ? row[0] : 0u;
+        bad |= ft > 4;
+        uint32_t mine = 0, up_prev = 0;          // this lane's last pixel / last row-above pixel
+        uint32_t q0 = 0, q1 = 0, q2 = 0;         // the last four RGB pixels, oldest in q0's low bytes
+        // as in k_png_unfilter: every lane loads every step of a chunk one chunk ahead (address
+        // clamped into the row, the value selected after).  The load is the 4 bytes at the pixel
+        // (rows are bpp W + 1 bytes: unaligned); for bpp < 4 it runs into the next row or, at the end
+        // of a file's block, into the block's padding (bpp W + 1 <= 4 W) -- those bytes are masked
+        auto ld = [&](int x) -> uint32_t {
+            const int xc = x < 0 ? 0 : (x >= W ? W - 1 : x);
+            return reinterpret_cast<const PngU32*>(row + 1 + (uint64_t)bpp * xc)->v;
+        };
+        auto fix = [&](uint32_t (&v)[8], int x0) {
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]),
+                         "+v"(v[7]));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int x = x0 + j;
+                v[j] = (valid && x >= 0 && x < W) ? (v[j] & keep) : 0u;
+            }
+        };
+        uint32_t cur[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) cur[j] = ld(j - lane);
+        fix(cur, -lane);
+        for (int t0 = 0; t0 < W + 63; t0 += 8) {
+            uint32_t nxt[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) nxt[j] = ld(t0 + 8 + j - lane);     // fixed up next chunk
+            // lane 0's row above for the chunk (the previous band's last row), read ahead of the chain
+            uint32_t pv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pv[j] = prev[t0 + j < W ? t0 + j : 0];
+            asm volatile("" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]), "+v"(pv[4]), "+v"(pv[5]),
+                         "+v"(pv[6]), "+v"(pv[7]));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pv[j] = (b0 > 0 && t0 + j < W) ? pv[j] : 0u;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int x = t0 + j - lane;
+                const bool act = valid && x >= 0 && x < W;
+                // the row above = lane - 1's pixel of the previous step: a one-lane shift (DPP wave_shr:1)
+                const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x138, 0xf, 0xf, true);
+                const uint32_t up = lane == 0 ? pv[j] : nb;
+                const uint32_t left = x > 0 ? mine : 0u;
+                const uint32_t ul = x > 0 ? up_prev : 0u;
+                uint32_t o = 0;
+                if (act) {
+#pragma unroll
+                    for (int k = 0; k < 32; k += 8)
+                        o |= ((((cur[j] >> k) & 255u) +
+                               png_pred(ft, (left >> k) & 255u, (up >> k) & 255u, (ul >> k) & 255u)) & 255u) << k;
+                    const uint32_t px = grey ? (o & 255u) * 0x010101u : (o & 0xffffffu);
+                    q0 = __builtin_amdgcn_alignbit(q1, q0, 24);
+                    q1 = __builtin_amdgcn_alignbit(q2, q1, 24);
+                    q2 = (q2 >> 24) | (px << 8);
+                    uint8_t* d = dst + ((uint64_t)r * W + (x & ~3)) * 3;
+                    if ((x & 3) == 3) {
+                        *reinterpret_cast<PngU96*>(d) = PngU96{q0, q1, q2};
+                    } else if (x == W - 1) {         // the row's last 1 to 3 pixels: byte stores
+                        const int n = (x & 3) + 1;
+                        for (int i = n; i < 4; ++i) {
+                            q0 = __builtin_amdgcn_alignbit(q1, q0, 24);
+                            q1 = __builtin_amdgcn_alignbit(q2, q1, 24);
+                            q2 >>= 24;
+                        }
+                        for (int i = 0; i < 3 * n; ++i)
+                            d[i] = (uint8_t)((i < 4 ? q0 : (i < 8 ? q1 : q2)) >> (8 * (i & 3)));
+                    }
+                    if (lane == 63) prev[x] = o;
+                }
+                mine = o;
+                up_prev = up;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) cur[j] = nxt[j];
+            fix(cur, t0 + 8 - lane);
+        }
+        __syncthreads();
+    }
+    if (__any(bad) && lane == 0) status[f] |= BF_PNG_BAD_FILTER;
+}
+
+// ---- host --------------------------------------------------------------------------------------
+static size_t png_workspace(int F, int H, int W, int bpp, long long total_file_bytes) {
     if (F < 0 || H <= 0 || W <= 0 || total_file_bytes < 0) return 0;
     return png_tab_bytes(F) + png_list_bytes(F, total_file_bytes) + png_z_bytes(F, total_file_bytes) +
-           png_align((size_t)F * png_rstride(H, W) + 16, 256);
+           png_align((size_t)F * png_rstride(H, W, bpp) + 16, 256);
+}
+
+BF_API size_t bf_png_workspace_bytes(int F, int H, int W, long long total_file_bytes) {
+    return png_workspace(F, H, W, 2, total_file_bytes);
+}
+
+BF_API size_t bf_png_rgb_workspace_bytes(int F, int H, int W, long long total_file_bytes) {
+    return png_workspace(F, H, W, 4, total_file_bytes);
+}
+
+// the launches every entry point shares: chunk walk (accepting kKind), IDAT gather, inflate into
+// the filtered rows (file f at rows + f * fstride; kBpp = the widest pixel of kKind)
+struct PngRows {
+    int rc;
+    const PngSegTable* tabs;
+    const uint8_t* rows;
+    uint64_t fstride;
+};
+template <int kKind, int kBpp>
+static PngRows png_inflate_rows(const uint8_t* files, const int64_t* offsets, int F, int H, int W,
+                                long long total_file_bytes, long long max_file_bytes, const void* out, void* work,
+                                size_t work_bytes, int32_t* status, hipStream_t s) {
+    PngRows R{BF_OK, nullptr, nullptr, 0};
+    if (!files || !offsets || !out || !work || !status || F < 0 || H <= 0 || W <= 0 || total_file_bytes < 0 ||
+        max_file_bytes < 0)
+        R.rc = BF_ERR_ARG;
+    else if (W > 4096 || (uint64_t)H * (kBpp * (uint64_t)W + 1) >= (1ull << 31) || max_file_bytes >= (1ll << 31))
+        R.rc = BF_ERR_UNSUPPORTED;
+    else if (work_bytes < png_workspace(F, H, W, kBpp, total_file_bytes))
+        R.rc = BF_ERR_CAPACITY;
+    if (R.rc != BF_OK || F == 0) return R;
+    uint8_t* w = static_cast<uint8_t*>(work);
+    PngSegTable* tabs = reinterpret_cast<PngSegTable*>(w);
+    PngSeg* segs = reinterpret_cast<PngSeg*>(w + png_tab_bytes(F));
+    uint8_t* z = w + png_tab_bytes(F) + png_list_bytes(F, total_file_bytes);
+    uint8_t* rows = z + png_z_bytes(F, total_file_bytes);
+    R.tabs = tabs;
+    R.rows = rows;
+    R.fstride = png_rstride(H, W, kBpp);
+    hipLaunchKernelGGL(k_png_parse<kKind>, dim3(F), dim3(64), 0, s, files, offsets, F, H, W, tabs, segs, status);
+    const unsigned gx = (unsigned)((max_file_bytes + 16 + 256 * 16 - 1) / (256 * 16));
+    hipLaunchKernelGGL(k_png_gather, dim3(gx ? gx : 1, F), dim3(256), 0, s, files, offsets, tabs, segs, z);
+    hipLaunchKernelGGL(k_png_inflate, dim3(F), dim3(64), 0, s, z, offsets, tabs, H, R.fstride, rows, status);
+    return R;
 }
 
 template <typename OutT>
 static int png_decode(const uint8_t* files, const int64_t* offsets, int F, int H, int W, long long total_file_bytes,
                       long long max_file_bytes, float depth_scale, OutT* out, void* work, size_t work_bytes,
                       int32_t* status, void* stream) {
-    if (!files || !offsets || !out || !work || !status || F < 0 || H <= 0 || W <= 0 || total_file_bytes < 0 ||
-        max_file_bytes < 0 || !(depth_scale > 0.f))
-        return BF_ERR_ARG;
-    if (W > 4096 || (uint64_t)H * (2 * (uint64_t)W + 1) >= (1ull << 31) || max_file_bytes >= (1ll << 31))
-        return BF_ERR_UNSUPPORTED;
-    if (work_bytes < bf_png_workspace_bytes(F, H, W, total_file_bytes)) return BF_ERR_CAPACITY;
-    if (F == 0) return BF_OK;
-    uint8_t* w = static_cast<uint8_t*>(work);
-    PngSegTable* tabs = reinterpret_cast<PngSegTable*>(w);
-    PngSeg* segs = reinterpret_cast<PngSeg*>(w + png_tab_bytes(F));
-    uint8_t* z = w + png_tab_bytes(F) + png_list_bytes(F, total_file_bytes);
-    uint8_t* rows = z + png_z_bytes(F, total_file_bytes);
+    if (!(depth_scale > 0.f)) return BF_ERR_ARG;
     hipStream_t s = bf_stream(stream);
-    hipLaunchKernelGGL(k_png_parse, dim3(F), dim3(64), 0, s, files, offsets, F, H, W, tabs, segs, status);
-    const unsigned gx = (unsigned)((max_file_bytes + 16 + 256 * 16 - 1) / (256 * 16));
-    hipLaunchKernelGGL(k_png_gather, dim3(gx ? gx : 1, F), dim3(256), 0, s, files, offsets, tabs, segs, z);
-    hipLaunchKernelGGL(k_png_inflate, dim3(F), dim3(64), 0, s, z, offsets, tabs, H, W, rows, status);
-    hipLaunchKernelGGL(k_png_unfilter<OutT>, dim3(F), dim3(64), 0, s, rows, H, W, depth_scale, out, status);
+    const PngRows R = png_inflate_rows<PNG_GREY16, 2>(files, offsets, F, H, W, total_file_bytes, max_file_bytes, out,
+                                                      work, work_bytes, status, s);
+    if (R.rc != BF_OK || F == 0) return R.rc;
+    hipLaunchKernelGGL(k_png_unfilter<OutT>, dim3(F), dim3(64), 0, s, R.rows, H, W, R.fstride, depth_scale, out,
+                       status);
     return bf_check_launch();
 }
 
@@ -854,3 +1016,15 @@ BF_API int bf_png_decode_depth(const uint8_t* files, const int64_t* offsets, int
     return png_decode(files, offsets, F, H, W, total_file_bytes, max_file_bytes, depth_scale, depth_out, work,
                       work_bytes, status, stream);
 }
+
+BF_API int bf_png_decode_rgb(const uint8_t* files, const int64_t* offsets, int F, int H, int W,
+                             long long total_file_bytes, long long max_file_bytes, uint8_t* rgb, void* work,
+                             size_t work_bytes, int32_t* status, void* stream) {
+    hipStream_t s = bf_stream(stream);
+    const PngRows R = png_inflate_rows<PNG_COLOUR8, 4>(files, offsets, F, H, W, total_file_bytes, max_file_bytes, rgb,
+                                                       work, work_bytes, status, s);
+    if (R.rc != BF_OK || F == 0) return R.rc;
+    hipLaunchKernelGGL(k_png_unfilter_rgb8, dim3(F), dim3(64), 0, s, R.rows, R.tabs, H, W, R.fstride, rgb, status);
+    return bf_check_launch();
+}
+

@@ -627,12 +627,15 @@ int bf_cv2_resize_u8(const uint8_t* src, int Hs, int Ws, int cn, int Hd, int Wd,
  * caller-owned device memory. */
 #define BF_PNG_BAD_SIGNATURE 1
 #define BF_PNG_BAD_HEADER 2      /* IHDR missing / invalid */
-#define BF_PNG_UNSUPPORTED 4     /* not 16-bit greyscale non-interlaced, or an unknown critical chunk */
+#define BF_PNG_UNSUPPORTED 4     /* not an image kind of the entry point (bf_png_decode_u16 / _depth: 16-bit
+                                  * greyscale; bf_png_decode_rgb: 8-bit grey / RGB / grey + alpha / RGBA; all
+                                  * non-interlaced), or an unknown critical chunk */
 #define BF_PNG_BAD_CHUNK 8       /* truncated chunk, no IDAT, a zlib stream of 2 GiB or more */
 #define BF_PNG_BAD_ZLIB 16       /* invalid zlib header / deflate block / code / distance */
 #define BF_PNG_BAD_ADLER 32
 #define BF_PNG_BAD_FILTER 64     /* row filter type > 4 */
-#define BF_PNG_SIZE 128          /* IHDR size != (W, H) or inflated length != H x (2W + 1) */
+#define BF_PNG_SIZE 128          /* IHDR size != (W, H) or inflated length != H x (bpp W + 1), bpp the file's
+                                  * bytes per pixel (2 for 16-bit grey; 1 / 3 / 2 / 4 for the 8-bit kinds) */
 size_t bf_png_workspace_bytes(int F, int H, int W, long long total_file_bytes);
 int bf_png_decode_u16(const uint8_t* files, const int64_t* offsets, int F, int H, int W,
                       long long total_file_bytes, long long max_file_bytes, uint16_t* out, void* work,
@@ -642,6 +645,19 @@ int bf_png_decode_u16(const uint8_t* files, const int64_t* offsets, int F, int H
 int bf_png_decode_depth(const uint8_t* files, const int64_t* offsets, int F, int H, int W,
                         long long total_file_bytes, long long max_file_bytes, float depth_scale,
                         float* depth_out, void* work, size_t work_bytes, int32_t* status, void* stream);
+
+/* ---- colour PNG decode (reference: cv2.imread(color_path) + cvtColor(BGR2RGB),
+ * capture_stream.py:402 CA-1M, the PNG files of its rgb/ folder) ----
+ * F PNG files laid out as above, each exactly H x W, 8 bits per sample, non-interlaced: greyscale,
+ * RGB, greyscale + alpha or RGBA (a batch may mix them) -> rgb u8 [F,H,W,3] in RGB order, the layout
+ * of bf_jpeg_decode_rgb; grey is replicated, alpha dropped, a tRNS chunk ignored (cv2's default flag
+ * strips transparency).  Palette, 16-bit and sub-byte files, 16-bit greyscale included, and Adam7
+ * report BF_PNG_UNSUPPORTED.  status and the checks as for bf_png_decode_u16; W <= 4096 and
+ * H x (4W + 1) < 2^31.  work: bf_png_rgb_workspace_bytes(F, H, W, total_file_bytes) bytes. */
+size_t bf_png_rgb_workspace_bytes(int F, int H, int W, long long total_file_bytes);
+int bf_png_decode_rgb(const uint8_t* files, const int64_t* offsets, int F, int H, int W,
+                      long long total_file_bytes, long long max_file_bytes, uint8_t* rgb,
+                      void* work, size_t work_bytes, int32_t* status, void* stream);
 
 /* ---- colour JPEG decode (reference: cv2.imread(color_path), capture_stream.py:194 ScanNet /
  * :402 CA-1M -- libjpeg's default decompression, which PIL's decoder reproduces) ----
