@@ -434,13 +434,16 @@ BF_API int bf_row_heads_f32(const float* x, int ldx, int in_fs, int in_off, int 
 // ------------------------------------------------------------------------------------------
 // per-frame top-k: values v[(f*n + i)*ldv] (i < n <= 4096), bitonic sort of (value, index) in LDS,
 // descending by value, ties -> lower index first (NaN sorts last); idx[f*k + j] (int32), vals.
+// The order is total: non-NaN before NaN, descending by value, equal values (or two NaNs) by
+// ascending index.  The power-of-two padding is NaN with indices >= n, so it sorts strictly after
+// every real entry, NaN included, and the first k <= n sorted indices are always real ones.
 // ------------------------------------------------------------------------------------------
 #define TK_MAX 4096
 __device__ __forceinline__ bool dn_before(float va, int ia, float vb, int ib) {
     // a sorts before b
     const bool na = va != va, nb = vb != vb;
     if (na != nb) return nb;
-    if (va != vb) return va > vb;
+    if (!na && va != vb) return va > vb;
     return ia < ib;
 }
 
@@ -469,7 +472,7 @@ __global__ void __launch_bounds__(1024) k_topk_rows(const float* __restrict__ v,
     __shared__ int si[TK_MAX];
     const int f = blockIdx.x;
     for (int i = threadIdx.x; i < n2; i += blockDim.x) {
-        sv[i] = i < n ? v[((size_t)f * n + i) * ldv] : -INFINITY;
+        sv[i] = i < n ? v[((size_t)f * n + i) * ldv] : __builtin_nanf("");
         si[i] = i < n ? i : n + i;
     }
     __syncthreads();
@@ -567,7 +570,7 @@ __global__ void __launch_bounds__(1024) k_infer_select(DnInferArgs a) {
             sv[i] = 1.f / (1.f + expf(-x));
             si[i] = i;
         } else {
-            sv[i] = -INFINITY;
+            sv[i] = __builtin_nanf("");   // padding: after every real entry (index i >= n)
             si[i] = i;
         }
     }
