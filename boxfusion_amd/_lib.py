@@ -575,7 +575,8 @@ ACT = {None: 0, "none": 0, "gelu": 1, "relu": 2}
 class GemmPlan(ctypes.Structure):
     """bf_gemm_plan: per-call GEMM options (include/boxfusion_hip.h); all-zero = product defaults"""
     _fields_ = [("cu_budget", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("kernel", ctypes.c_int32),
-                ("variant", ctypes.c_int32), ("group_m", ctypes.c_int32), ("balanced", ctypes.c_int32)]
+                ("variant", ctypes.c_int32), ("group_m", ctypes.c_int32), ("balanced", ctypes.c_int32),
+                ("objective", ctypes.c_int32)]
 
 
 # The CU budget a thread's GEMMs pass in their plan (0 = every CU).  Host-side, per thread: the C
@@ -615,6 +616,23 @@ def _plan(plan):
     elif isinstance(plan, dict):
         plan = GemmPlan(**{"cu_budget": cu_budget(), **plan})
     return ctypes.byref(plan)
+
+
+def gemm_tile_rows(M, N, K, plan=None):
+    """tile height the persistent bf16 GEMM takes for this shape under `plan` (as gemm()'s plan
+    argument); host-only, needs no GPU"""
+    r = lib().bf_gemm_tile_rows_plan(c_int(M), c_int(N), c_int(K), _plan(plan))
+    if r <= 0:
+        raise HipError(f"bf_gemm_tile_rows_plan failed with bf_status {r}")
+    return r
+
+
+def gemm_grid(M, N, K, plan=None):
+    """workgroups of the persistent grid at that height (CU-time = this x the GEMM's duration)"""
+    r = lib().bf_gemm_grid_plan(c_int(M), c_int(N), c_int(K), _plan(plan))
+    if r <= 0:
+        raise HipError(f"bf_gemm_grid_plan failed with bf_status {r}")
+    return r
 
 
 def gemm(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype=torch.bfloat16,

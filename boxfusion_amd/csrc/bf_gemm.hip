@@ -1285,6 +1285,7 @@ struct GemmCfg {
                      // across ranks whatever their budgets)
     int n_cu;        // CUs the persistent grid and the tile-height model assume (the budget)
     int tile_rows;   // 0 = the per-shape model
+    int objective;   // the model's objective: 0 = throughput (CU-time), 1 = latency (rounds)
     int kernel;      // 0 = the shape rule, 1 = 128x128 tiles, -1 = the persistent kernels
     int variant;     // 1..6 (above)
     int group_m;     // row panels per tile group (tile_coords); 1 = row-major
@@ -1309,6 +1310,7 @@ static GemmCfg gemm_cfg(const bf_gemm_plan* p) {
     c.n_cu_dev = gemm_device_cus();
     c.n_cu = (p && p->cu_budget > 0 && p->cu_budget < c.n_cu_dev) ? p->cu_budget : c.n_cu_dev;
     c.tile_rows = (p && p->tile_rows >= 160 && p->tile_rows <= 256 && p->tile_rows % 32 == 0) ? p->tile_rows : 0;
+    c.objective = (p && p->objective == 1) ? 1 : 0;
     c.kernel = p ? (p->kernel > 0 ? 1 : p->kernel < 0 ? -1 : 0) : 0;
     c.variant = (p && p->variant >= 1 && p->variant <= 6) ? p->variant : 5;
     c.group_m = (p && p->group_m > 0) ? p->group_m : 8;
@@ -1367,12 +1369,21 @@ static int gemm_grid(long long tiles, const GemmCfg& cfg) {
     return grid;
 }
 
-// Tile height of k_gemm256q for an M x N x K problem, from the shape (and the grid's CU count):
-// the height with the lowest rounds(BM) x t(BM), rounds = ceil(tiles / CUs), t(BM) the per-tile
-// time model above.  Against the sweep of every path shape (profiles/r05_gemm_tile_sweep.log) it
-// picks the fastest height or one within 1 %: 224 rows for CLIP proj / fc2 (N = 1280) and CuTR's
-// window qkv, 160 for CuTR's N = 768 residual GEMMs, 256 elsewhere.  Every height gives the same
-// K-order MFMA chain per output, so this choice never changes a value.
+// Tile height of k_gemm256q for an M x N x K problem, t(BM) the per-tile time model above.  Every
+// height gives the same K-order MFMA chain per output, so this choice never changes a value.
+//
+// Objective 1 (latency): the height with the lowest rounds(BM) x t(BM), rounds = ceil(tiles / CUs
+// of the budget): the duration of the GEMM running alone.  Against the sweep of every path shape
+// (profiles/r05_gemm_tile_sweep.log) it picks the fastest height or one within 1 %: 224 rows for
+// CLIP proj / fc2 (N = 1280) and CuTR's window qkv, 160 for CuTR's N = 768 residual GEMMs, 256
+// elsewhere.
+//
+// Objective 0 (throughput, the default): the lowest tiles(BM) x t(BM), the GEMM's CU-time.  A
+// persistent workgroup fills its CU (160 KB of LDS), so concurrent streams share the chip by whole
+// CUs and what a GEMM costs the pipeline is workgroups x duration, not its own latency (DESIGN.md
+// §4).  The fixed part of t(BM) makes this 256 rows wherever the rows fill the tiles (every path
+// shape); a shorter tile wins only where it trims the padding of a short M.  Reads the shape
+// alone, never the CU budget.
 static int gemm_tile_mb1(int M, int N, int K, const GemmCfg& cfg) {
     if (cfg.tile_rows) return (cfg.tile_rows / 2 - 64) / 16;
     const int n_cu = cfg.n_cu;
@@ -1382,12 +1393,25 @@ static int gemm_tile_mb1(int M, int N, int K, const GemmCfg& cfg) {
     for (int mb1 = 4; mb1 >= 1; --mb1) {
         const int bm = 2 * (64 + 16 * mb1);
         const long long tiles = ((M + bm - 1) / bm) * tn;
-        const long long rounds = (tiles + n_cu - 1) / n_cu;
-        const double cost = (double)rounds * (GEMM_TILE_FIXED + (1.0 - GEMM_TILE_FIXED) * bm / 256.0);
+        const long long units = cfg.objective == 1 ? (tiles + n_cu - 1) / n_cu : tiles;
+        const double cost = (double)units * (GEMM_TILE_FIXED + (1.0 - GEMM_TILE_FIXED) * bm / 256.0);
         if (mb1 == 4 || cost < best_cost) { best = mb1; best_cost = cost; }
     }
     (void)K;
     return best;
+}
+
+BF_API int bf_gemm_tile_rows_plan(int M, int N, int K, const bf_gemm_plan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0) return BF_ERR_ARG;
+    return 2 * (64 + 16 * gemm_tile_mb1(M, N, K, gemm_cfg(plan)));
+}
+
+// workgroups of the persistent grid at that height (the CU-time probes: CU-time = this x duration)
+BF_API int bf_gemm_grid_plan(int M, int N, int K, const bf_gemm_plan* plan) {
+    if (M <= 0 || N <= 0 || K <= 0) return BF_ERR_ARG;
+    const GemmCfg cfg = gemm_cfg(plan);
+    const int bm = 2 * (64 + 16 * gemm_tile_mb1(M, N, K, cfg));
+    return gemm_grid((long long)((M + bm - 1) / bm) * ((N + 255) / 256), cfg);
 }
 
 template <bool OB, int AC, bool RS, int F8, int MB1>
@@ -1620,15 +1644,17 @@ BF_API int bf_gemm_bf16_plan(const void* A, int lda, const void* W, int ldw, con
         const int grid2 = gemm_grid(t2, cfg);
         // the overlapped-epilogue kernel: plain / in-place residual outputs, >= 3 K-tiles, the bias
         // row fits its LDS slot, 32-bit byte offsets into C and the residual.  Variant 5 (default):
-        // bf16 outputs, and the f32 residual GEMMs whose tile height (gemm_tile_rows) is below 256;
-        // at 256 rows those measured 1-4 % slower on it than on k_gemm256p.  Variant 6: every
-        // eligible shape.
+        // bf16 outputs, and the f32 GEMMs whose tile height (gemm_tile_mb1) is below 256; at 256
+        // rows those measured 1-4 % slower on it than on k_gemm256p.  Under the throughput
+        // objective the f32 residual GEMMs stay on it at 256 rows too: the two kernels agree to
+        // rel_err < 1e-6, not to the bit, and these GEMMs ran it (at 160 / 224 rows) before the
+        // objective existed, so the path's values do not move.  Variant 6: every eligible shape.
         const int mb1 = gemm_tile_mb1(M, N, K, cfg);
         const bool q_fit = row_map == nullptr && resid_mod <= 0 && K / 64 >= 3 && N <= G2Q_BIAS_MAX && act <= 1 &&
                            !(resid && act) && !(resid && c_bf16) && !(act && !c_bf16) &&
                            (long long)(M - 1) * ldc * (c_bf16 ? 2 : 4) + (long long)N * 4 < (1LL << 31) &&
                            (!resid || (long long)(M - 1) * ldr * 4 + (long long)N * 4 < (1LL << 31));
-        const bool q_ok = q_fit && (cfg.variant == 6 || (cfg.variant == 5 && (c_bf16 || mb1 < 4)));
+        const bool q_ok = q_fit && (cfg.variant == 6 || (cfg.variant == 5 && (c_bf16 || mb1 < 4 || (cfg.objective == 0 && resid))));
         if (q_ok) {
             const int bm = 2 * (64 + 16 * mb1);
             const int tqm = (M + bm - 1) / bm;
@@ -1699,7 +1725,8 @@ BF_API int bf_gemm_fp8_plan(const void* A, int lda, const void* W, int ldw, floa
                             const float* bias, const float* resid, int ldr, void* C, int ldc, int out_kind,
                             float out_qscale, int M, int N, int K, int act, const bf_gemm_plan* plan,
                             void* stream) {
-    const GemmCfg cfg = gemm_cfg(plan);
+    GemmCfg cfg = gemm_cfg(plan);
+    cfg.objective = 1;   // the fp8 GEMMs keep the latency model's heights (plan->objective is not read)
     if (!A || !W || !C || !(scale > 0.f) || M < 0 || N <= 0 || K <= 0 || act < 0 || act > 1 ||
         out_kind < 0 || out_kind > 2)
         return BF_ERR_ARG;

@@ -362,7 +362,7 @@ int bf_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bi
  * only, the same on every box and every rank): few-row problems (the 128 x 128 tiling would feed
  * fewer than half the CUs; N % 32 == 0, K % 256 == 0) run k_gemm_skinny (8 waves split K, partials
  * summed in wave order); large ones the persistent kernels with a tile height of 160 / 192 / 224 /
- * 256 rows picked by the round quantisation of the walk (the height never changes a value).
+ * 256 rows picked by the plan's objective (below; the height never changes a value).
  *
  * bf_gemm_plan: caller-owned, per-call configuration (no process-wide GEMM state exists; NULL or an
  * all-zero plan = the product defaults):
@@ -370,12 +370,22 @@ int bf_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bi
  *              CU-masked stream passes that stream's CU count.  Sizes the grid and the tile-height
  *              model only, so results are bit-identical under any budget.
  *   tile_rows  0 = the per-shape model; 160 / 192 / 224 / 256 force the height (value-invariant).
+ *   objective  what the per-shape tile-height model minimises (bf_gemm_bf16_plan; the fp8 entry
+ *              point always uses 1).  0 (default) = throughput: the GEMM's CU-time, tiles(BM) x
+ *              t(BM), the cost to a pipeline whose streams share the chip by whole CUs; it reads
+ *              the shape alone (never cu_budget) and returns 256 rows for every path shape, and the
+ *              f32 residual GEMMs stay on k_gemm256q at that height.  1 = latency: rounds(BM) x
+ *              t(BM) on the budget's CUs, the duration of the GEMM running alone (160 / 224 rows
+ *              for CuTR's / CLIP's N = 768 / 1280 residual GEMMs).  Value-invariant within a kernel.
+ *              (The last field of the struct: a caller compiled against the six-field layout
+ *              must be rebuilt.)
  *   The remaining fields are measurement / test hooks (0 = product default):
  *   kernel     1 forces the 128x128 kernel, -1 the persistent kernels (aligned shapes);
  *   variant    persistent kernel variant: 1 = k_gemm256p (staggered 4-phase schedule), 2 = k_gemm256p
  *              unstaggered, 3 / 4 = timing ablations (no epilogue / no global stores: wrong
- *              results), 5 = default (k_gemm256q for bf16 outputs and sub-256-row residual tiles,
- *              k_gemm256p otherwise), 6 = k_gemm256q for every eligible shape;
+ *              results), 5 = default (k_gemm256q for bf16 outputs, for f32 residual outputs under
+ *              objective 0 and for sub-256-row f32 tiles under objective 1, k_gemm256p otherwise),
+ *              6 = k_gemm256q for every eligible shape;
  *   group_m    row panels per tile group of the persistent tile order (default 8; 1 = row-major);
  *   balanced   0 = default (ceil(tiles / rounds) workgroups when the last round is at least a
  *              quarter full), 1 = one workgroup per CU, 2 = balanced for every multi-round problem.
@@ -387,6 +397,7 @@ typedef struct {
     int32_t variant;
     int32_t group_m;
     int32_t balanced;
+    int32_t objective;
 } bf_gemm_plan;
 int bf_gemm_bf16_plan(const void* A, int lda, const void* W, int ldw, const float* bias,
                       const float* resid, int ldr, int resid_mod, void* C, int ldc, int c_bf16,
@@ -396,6 +407,12 @@ int bf_gemm_bf16_plan(const void* A, int lda, const void* W, int ldw, const floa
  * (k_gemm256p/q) under the default plan, 0 if the 128x128 one (k_gemm) -- lets profilers
  * attribute launches to kernels. */
 int bf_gemm_large_tiles(int M, int N, int K);
+/* Tile height (160 / 192 / 224 / 256 rows) the persistent k_gemm256q kernel takes for an M x N x K
+ * bf16 problem under `plan` (NULL = defaults): tile_rows if forced, else the objective's model.
+ * Host-only: launches nothing and needs no GPU (without one the device counts as 256 CUs). */
+int bf_gemm_tile_rows_plan(int M, int N, int K, const bf_gemm_plan* plan);
+/* workgroups of the persistent grid at that height (a GEMM's CU-time = this x its duration) */
+int bf_gemm_grid_plan(int M, int N, int K, const bf_gemm_plan* plan);
 
 /* fp8 e4m3 (OCP) GEMM of the CLIP ViT-H fp8 path (BASELINE configs[4]; the same open_clip
  * in_proj / c_fc / c_proj linears as bf_gemm_bf16, tools/utils.py:383-403):
