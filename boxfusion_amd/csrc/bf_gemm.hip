@@ -872,6 +872,16 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256p(const u16* __restric
 // Needs nk >= 3 K-tiles, N <= 8192 (bias row in LDS), no row map / broadcast residual; the host
 // falls back to k_gemm256p otherwise.
 //
+// The walk is tile -> K-tiles with four copies of the K-tile body (KTILE): the first K-tile of a
+// tile, a loop over the K-tiles 1 .. nk - 3 whose body has no branch and no address arithmetic
+// beyond a scalar K offset and the stage toggle (163 instructions for 64 MFMAs, 27 of them scalar
+// ALU and 6 vector ALU: profiles/gemm_kstep_isa_new.txt), K-tile nk - 2, which starts staging the
+// next tile, and the last K-tile.  Everything per tile (tile coordinates, the staging rows'
+// offsets, the epilogues' row and column offsets) is computed in the peeled bodies; one flat loop
+// testing "first" / "last" on every K-tile cost 67 scalar instructions per K-tile and ran 8-12 %
+// slower.  The order of phases, reads, staging and counted waits is the same in
+// every copy, and so is every output's MFMA chain.
+//
 // Measured (scripts/gemm_bench.py, interleaved in one process): bf16 outputs gain 6-16 % (CLIP
 // fc1+GELU 444.6 -> 397.2 us, qkv 278.2 -> 253.2, CuTR fc1 145.7 -> 123.0); the f32 residual
 // GEMMs do not (CLIP fc2 400.1 vs 406.5, proj 139.5 vs 141.9), so those keep k_gemm256p by
@@ -938,7 +948,8 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
     constexpr int R0 = RES ? 8 : 0, R1 = RES ? 2 * MB1 : 0;
     const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 2, wc = wave & 3;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int wr = wave_u >> 2, wc = wave_u & 3;      // wave-uniform: scalar registers
     const int lr = lane & 15, lq = lane >> 4;
     const int ntiles = tiles_m * tiles_n;
     const int G = gridDim.x;
@@ -951,7 +962,6 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
     unsigned long long st_t0 = 0, st_r0 = 0;
     if (t == 0) { st_t0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
 #endif
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
     // bias row -> LDS (retired with K-tile 0 by the prologue's counted wait)
     const float* bias_lds = reinterpret_cast<const float*>(g_smem + G2_STAGES_BYTES);
@@ -962,57 +972,45 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
         for (int n = t; n < N; n += G2_THREADS) reinterpret_cast<float*>(g_smem + G2_STAGES_BYTES)[n] = 0.f;
     }
 
-    int a_row[2][2], b_row[2][2], scol[2];
-    bool a1_ok[2];        // this lane's A-half-1 staging row lies inside the tile (MB1 < 4)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int L = (wave * 2 + i) * 8 + (lane >> 3);
-        scol[i] = ((lane & 7) ^ swz_key(L)) * 16;
-        a1_ok[i] = (L & 63) < 16 * MB1;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            a_row[h][i] = (L >> 6) * BMH + h * 64 + (L & 63);
-            b_row[h][i] = (L >> 5) * 64 + h * 32 + (L & 31);
-        }
-    }
     const int bytesA = (int)(((size_t)(M - 1) * lda + K) * ESZ);
     const int bytesW = (int)(((size_t)(N - 1) * ldw + K) * ESZ);
-    struct KT { int idx, m0, n0, k0, buf; };
-    auto kt_at_tile = [&](int tile_k, int idx) {
-        const int tile = slot + tile_k * G;
-        KT r;
-        r.idx = idx; tile_coords(tile, tiles_m, tiles_n, gm, r.m0, r.n0, 2 * BMH); r.k0 = 0; r.buf = idx & 1;
-        return r;
-    };
-    int tile_ord = 0;
-    auto kt_next = [&](KT c) {
-        if (c.idx >= total - 1) return c;
-        if (c.k0 + KTE < K) { c.k0 += KTE; c.idx += 1; c.buf ^= 1; return c; }
-        ++tile_ord;
-        return kt_at_tile(tile_ord, c.idx + 1);
-    };
+    // per-lane row byte offsets of the tile at (m0_, n0_): a[h][i] A-half h row i, b[h][i] B-half.
+    // Wave w, instruction i fills local rows L = (2w + i) * 8 + lane / 8 of a half: tile row
+    // (L >> 6) * BMH + h * 64 + (L & 63) of A-half h, tile column (L >> 5) * 64 + h * 32 + (L & 31)
+    // of B-half h.  Built from an opaque copy of the thread index once per tile, so that nothing of
+    // it stays in registers across the K-tiles.
     struct VO { int a[2][2], b[2][2]; };
-    auto vo_of = [&](const KT& c) {
+    auto vo_of = [&](int m0_, int n0_) {
         VO v;
+        int t_ = t;
+        asm volatile("" : "+v"(t_));
+        const int lane_ = t_ & 63;
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
+        for (int i = 0; i < 2; ++i) {
+            const int L = (wave_u * 2 + i) * 8 + (lane_ >> 3);
+            const int scol = ((lane_ & 7) ^ swz_key(L)) * 16;
+            const bool a1_ok = (L & 63) < 16 * MB1;   // the A-half-1 row lies inside the tile (MB1 < 4)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                v.a[h][i] = (h == 1 && !a1_ok[i]) ? (int)0x80000000
-                                                  : min(c.m0 + a_row[h][i], M - 1) * lda * ESZ + scol[i];
-                v.b[h][i] = min(c.n0 + b_row[h][i], N - 1) * ldw * ESZ + scol[i];
+            for (int h = 0; h < 2; ++h) {
+                const int a_row = (L >> 6) * BMH + h * 64 + (L & 63);
+                const int b_row = (L >> 5) * 64 + h * 32 + (L & 31);
+                v.a[h][i] = (h == 1 && !a1_ok) ? (int)0x80000000 : min(m0_ + a_row, M - 1) * lda * ESZ + scol;
+                v.b[h][i] = min(n0_ + b_row, N - 1) * ldw * ESZ + scol;
             }
+        }
         return v;
     };
-#define STAGE_HALF(c, v, which)                                                                    \
+    // issue half `which` (0 A0, 1 A1, 2 B0, 3 B1) of the K-tile at byte offset `kb` of the rows `v`
+    // into stage `buf`
+#define STAGE_HALF(buf, v, kb, which)                                                              \
     if (!(GEMM_ABL & 1) || !in_loop_)                                                              \
     {                                                                                              \
-        unsigned char* dst_ = g_smem + (c).buf * 65536 + (which) * 16384 + wave_u * 2048;          \
+        unsigned char* dst_ = g_smem + (buf) * 65536 + (which) * 16384 + wave_u * 2048;            \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                         \
             if ((which) < 2)                                                                       \
-                glds_buf16(A, bytesA, dst_ + i_ * 1024, (v).a[(which) & 1][i_], (c).k0 * ESZ);     \
+                glds_buf16(A, bytesA, dst_ + i_ * 1024, (v).a[(which) & 1][i_], (kb));             \
             else                                                                                   \
-                glds_buf16(W, bytesW, dst_ + i_ * 1024, (v).b[(which) & 1][i_], (c).k0 * ESZ);     \
+                glds_buf16(W, bytesW, dst_ + i_ * 1024, (v).b[(which) & 1][i_], (kb));             \
         }                                                                                          \
     }
 
@@ -1035,22 +1033,27 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
                 acc[(MI) * 4 + i][(NI) * 2 + j] = (f32x4){0.f, 0.f, 0.f, 0.f};                     \
         }                                                                                          \
     }
+    // The tile-boundary code (epilogues, residual loads) takes its lane coordinates from an opaque
+    // copy of the thread index: its per-lane row and column offsets are then computed where they
+    // are used, four times per tile, instead of being kept in registers across the K-tiles.
+#define LANE_RQ() int t_ = t; asm volatile("" : "+v"(t_)); const int lr_ = t_ & 15, lq_ = (t_ >> 4) & 3
     // the same inside the K loop: the residual arrives by loads hidden from the compiler's waitcnt
     // pass (which would otherwise wait for nearly every outstanding operation before the next
     // MFMA on the quadrant), retired by the counted waits of the following phases
-#define QINIT_ASYNC(MI, NI, T_)                                                                    \
+#define QINIT_ASYNC(MI, NI, m0_, n0_)                                                              \
     {                                                                                              \
         if constexpr (RES) {                                                                       \
+            LANE_RQ();                                                                             \
             _Pragma("unroll") for (int i = 0; i < NBLK(MI); ++i) {                                \
-                const float* rp_ = resid + (size_t)min((T_).m0 + wr * BMH + (MI) * 64 + i * 16 + lr, M - 1) * ldr; \
+                const float* rp_ = resid + (size_t)min((m0_) + wr * BMH + (MI) * 64 + i * 16 + lr_, M - 1) * ldr; \
                 _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
                     asm volatile("global_load_dwordx4 %0, %1, off"                                 \
                                  : "=v"(acc[(MI) * 4 + i][(NI) * 2 + j])                           \
-                                 : "v"(rp_ + min((T_).n0 + wc * 64 + (NI) * 32 + j * 16 + 4 * lq, N - 4)) \
+                                 : "v"(rp_ + min((n0_) + wc * 64 + (NI) * 32 + j * 16 + 4 * lq_, N - 4)) \
                                  : "memory");                                                      \
             }                                                                                      \
         } else {                                                                                   \
-            QINIT(MI, NI, (T_).m0, (T_).n0);                                                       \
+            QINIT(MI, NI, m0_, n0_);                                                               \
         }                                                                                          \
     }
     // output buffer descriptor: byte offsets of rows < M only (the rest are dropped)
@@ -1060,14 +1063,15 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
     // epilogue of quadrant (MI, NI) of the tile at (em0_, en0_)
 #define QEPI(MI, NI, em0_, en0_)                                                                   \
     {                                                                                              \
-        const int cb_ = (en0_) + wc * 64 + (NI) * 32 + 4 * lq;                                     \
+        LANE_RQ();                                                                                 \
+        const int cb_ = (en0_) + wc * 64 + (NI) * 32 + 4 * lq_;                                    \
         const f32x4 b0_ = *reinterpret_cast<const f32x4*>(bias_lds + min(cb_, N - 4));            \
         const f32x4 b1_ = *reinterpret_cast<const f32x4*>(bias_lds + min(cb_ + 16, N - 4));       \
         _Pragma("unroll") for (int i = 0; i < NBLK(MI); ++i) {                                    \
-            const int r_ = (em0_) + wr * BMH + (MI) * 64 + i * 16 + lr;                            \
+            const int r_ = (em0_) + wr * BMH + (MI) * 64 + i * 16 + lr_;                           \
             if constexpr ((F8 & 2) != 0) {                                                         \
                 /* fp8 row segments, one block at a time (fewer live registers): 4 bytes per      \
-                   block, exchanged between lane rows -> 8 consecutive bytes */                     \
+                   block, exchanged between lane rows -> 8 consecutive bytes */                    \
                 int XY_[2];                                                                        \
                 _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                 \
                     f32x4 x_ = acc[(MI) * 4 + i][(NI) * 2 + jj] * csc + (jj ? b1_ : b0_);          \
@@ -1082,7 +1086,7 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
                     XY_[jj] = __builtin_amdgcn_cvt_pk_fp8_f32(x_.z, x_.w, q_, true);               \
                 }                                                                                  \
                 const auto s_ = __builtin_amdgcn_permlane16_swap((uint32_t)XY_[0], (uint32_t)XY_[1], false, false); \
-                const int c_ = (en0_) + wc * 64 + (NI) * 32 + 16 * (lq & 1) + 8 * (lq >> 1);        \
+                const int c_ = (en0_) + wc * 64 + (NI) * 32 + 16 * (lq_ & 1) + 8 * (lq_ >> 1);        \
                 const int off_ = (r_ < M && c_ < N && !(GEMM_ABL & 4)) ? (r_ * ldc + c_) : (int)0x80000000; \
                 __builtin_amdgcn_raw_buffer_store_b64((u32x2v){s_[0], s_[1]}, crs, off_, 0, 2);   \
                 continue;                                                                          \
@@ -1098,7 +1102,7 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
             if constexpr (ACT == 1) {                                                              \
                 f32x2 p0 = {x0.x, x0.y}, p1 = {x0.z, x0.w}, p2 = {x1.x, x1.y}, p3 = {x1.z, x1.w}; \
                 gelu_erf2x2(p0, p1); gelu_erf2x2(p2, p3);                                          \
-                x0 = (f32x4){p0.x, p0.y, p1.x, p1.y}; x1 = (f32x4){p2.x, p2.y, p3.x, p3.y};         \
+                x0 = (f32x4){p0.x, p0.y, p1.x, p1.y}; x1 = (f32x4){p2.x, p2.y, p3.x, p3.y};        \
             } else if constexpr (ACT == 2) {                                                       \
                 x0 = __builtin_elementwise_max(x0, (f32x4){0.f, 0.f, 0.f, 0.f});                   \
                 x1 = __builtin_elementwise_max(x1, (f32x4){0.f, 0.f, 0.f, 0.f});                   \
@@ -1109,7 +1113,7 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
                 uint32_t Y0 = pk_bf16(x1.x, x1.y), Y1 = pk_bf16(x1.z, x1.w);                       \
                 const auto s0_ = __builtin_amdgcn_permlane16_swap(X0, Y0, false, false);           \
                 const auto s1_ = __builtin_amdgcn_permlane16_swap(X1, Y1, false, false);           \
-                const int c_ = (en0_) + wc * 64 + (NI) * 32 + 16 * (lq & 1) + 8 * (lq >> 1);        \
+                const int c_ = (en0_) + wc * 64 + (NI) * 32 + 16 * (lq_ & 1) + 8 * (lq_ >> 1);        \
                 const int off_ = (r_ < M && c_ < N && !(GEMM_ABL & 4)) ? (r_ * ldc + c_) * 2 : (int)0x80000000; \
                 __builtin_amdgcn_raw_buffer_store_b128((u32x4v){s0_[0], s1_[0], s0_[1], s1_[1]},   \
                                                        crs, off_, 0, 2);                           \
@@ -1166,20 +1170,81 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
         if (GEMM_PRIO_MODE == 0) __builtin_amdgcn_s_setprio(0);                                    \
     }
 
+    // One K-tile: phases P1..P4 (Q00, Q01, Q11, Q10), each a memory section | barrier | MFMAs |
+    // barrier, reading stage `st` and restaging its halves with the K-tile two ahead of it in the
+    // walk: rows SV_, byte offset SKB_ along K, into stage SBUF_.  ISF_: first K-tile of a tile that
+    // follows another (the previous tile's Q10 epilogue in P1); ISL_: last K-tile of a tile (the
+    // epilogues of Q00, Q01, Q11 in P2..P4).  The walk below passes both as literal `false` for
+    // the K-tiles inside a tile, whose body is then straight-line code.
+#define KTILE(ISF_, ISL_, SV_, SKB_, SBUF_)                                                        \
+    {                                                                                              \
+        /* ---- P1: Q00; reads B0 then A0; [first K-tile: the previous tile's Q10] */              \
+        RD_B(fb0, gb0, st, 0);                                                                     \
+        SB0();                                                                                     \
+        RD_A(st, 0);                                                                               \
+        if (ISF_) {                                                                                \
+            QEPI(1, 0, em0, en0); QINIT_ASYNC(1, 0, cm0, cn0);                                     \
+            CBAR();                                                                                \
+            if constexpr (RES) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + S0 + R0 + 2 * (S1 + R1)) : "memory");  /* Q00's residual (L.P2) */ \
+        }                                                                                          \
+        CBAR();                                                                                    \
+        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");                                         \
+        PHASE_BARRIER();                                                                           \
+        MFMA_Q(0, 0, fb0, gb0);                                                                    \
+        PHASE_BARRIER();                                                                           \
+        /* ---- P2: Q01; reads B1; stage B0 of g+2; [last K-tile: Q00] */                          \
+        RD_B(fb1, gb1, st, 1);                                                                     \
+        STAGE_HALF(SBUF_, SV_, SKB_, 2);                                                           \
+        if (ISL_) { QEPI(0, 0, cm0, cn0); QINIT_ASYNC(0, 0, nm0, nn0); }                           \
+        if (ISF_) {                                                                                \
+            if constexpr (RES) { CBAR(); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + 2 * (S1 + R1)) : "memory"); }  /* Q01 (L.P3) */ \
+        }                                                                                          \
+        CBAR();                                                                                    \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                         \
+        PHASE_BARRIER();                                                                           \
+        MFMA_Q(0, 1, fb1, gb1);                                                                    \
+        PHASE_BARRIER();                                                                           \
+        /* ---- P3: Q11; reads A1; stage A0 of g+2; [last K-tile: Q01] */                          \
+        RD_A(st, 1);                                                                               \
+        STAGE_HALF(SBUF_, SV_, SKB_, 0);                                                           \
+        if (ISL_) { QEPI(0, 1, cm0, cn0); QINIT_ASYNC(0, 1, nm0, nn0); }                           \
+        if (ISF_) {                                                                                \
+            if constexpr (RES) { CBAR(); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + S1 + R1) : "memory"); }    /* Q11 (L.P4) */ \
+        }                                                                                          \
+        CBAR();                                                                                    \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                         \
+        PHASE_BARRIER();                                                                           \
+        MFMA_Q(1, 1, fb1, gb1);                                                                    \
+        PHASE_BARRIER();                                                                           \
+        /* ---- P4: Q10 from registers; stage B1 and A1 of g+2; [last K-tile: Q11]; retire g+1 */  \
+        STAGE_HALF(SBUF_, SV_, SKB_, 3);                                                           \
+        STAGE_HALF(SBUF_, SV_, SKB_, 1);                                                           \
+        if (ISL_) {                                                                                \
+            QEPI(1, 1, cm0, cn0); QINIT_ASYNC(1, 1, nm0, nn0);                                     \
+            CBAR();                                                                                \
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + 2 * (S0 + R0) + S1 + R1) : "memory");    \
+            em0 = cm0; en0 = cn0;                                                                  \
+        } else if (ISF_) {                                                                         \
+            /* K-tile g+1, and (RES) Q10's residual from P1: 8 younger LDS-DMA */                  \
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RES ? 8 : 8 + S1) : "memory");               \
+        } else {                                                                                   \
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                       \
+        }                                                                                          \
+        PHASE_BARRIER();                                                                           \
+        MFMA_Q(1, 0, fb0, gb0);                                                                    \
+        PHASE_BARRIER();                                                                           \
+        st ^= 1;                                                                                   \
+    }
+
     bool in_loop_ = false;    // GEMM_ABL diagnostics act inside the K loop only
-    KT kc = kt_at_tile(0, 0);
-    KT k1 = kt_next(kc);
-    KT k2 = kt_next(k1);
-    VO v2 = vo_of(k2);
-    QINIT(0, 0, kc.m0, kc.n0); QINIT(0, 1, kc.m0, kc.n0); QINIT(1, 1, kc.m0, kc.n0); QINIT(1, 0, kc.m0, kc.n0);
-    {
-        const VO v0 = vo_of(kc);
-        STAGE_HALF(kc, v0, 2); STAGE_HALF(kc, v0, 0); STAGE_HALF(kc, v0, 3); STAGE_HALF(kc, v0, 1);
-    }
-    {
-        const VO v1 = vo_of(k1);
-        STAGE_HALF(k1, v1, 2); STAGE_HALF(k1, v1, 0); STAGE_HALF(k1, v1, 3); STAGE_HALF(k1, v1, 1);
-    }
+    constexpr int KTB = KTE * ESZ;          // bytes along K per K-tile (128)
+    int cm0, cn0;             // the tile being accumulated
+    tile_coords(slot, tiles_m, tiles_n, gm, cm0, cn0, 2 * BMH);
+    VO v2 = vo_of(cm0, cn0);  // staging rows of K-tile g+2's tile
+    QINIT(0, 0, cm0, cn0); QINIT(0, 1, cm0, cn0); QINIT(1, 1, cm0, cn0); QINIT(1, 0, cm0, cn0);
+    // prologue: K-tiles 0 and 1 of the first tile (nk >= 3)
+    STAGE_HALF(0, v2, 0, 2); STAGE_HALF(0, v2, 0, 0); STAGE_HALF(0, v2, 0, 3); STAGE_HALF(0, v2, 0, 1);
+    STAGE_HALF(1, v2, KTB, 2); STAGE_HALF(1, v2, KTB, 0); STAGE_HALF(1, v2, KTB, 3); STAGE_HALF(1, v2, KTB, 1);
     asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
     PHASE_BARRIER();
     if (stagger && wr == 1) PHASE_BARRIER();
@@ -1188,71 +1253,22 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
     int em0 = 0, en0 = 0;     // the tile whose quadrant Q10 is still pending
     if (GEMM_ABL & 2) { RD_B(fb0, gb0, 0, 0); RD_B(fb1, gb1, 0, 1); RD_A(0, 0); }
     in_loop_ = true;
-    for (int g = 0; g < total; ++g) {
-        const int st = g & 1;
-        const bool isL = kc.k0 == K - KTE;
-        const bool isF = kc.k0 == 0 && g > 0;
-        // ---- P1: Q00; reads B0 then A0; [first K-tile: the previous tile's Q10]
-        RD_B(fb0, gb0, st, 0);
-        SB0();
-        RD_A(st, 0);
-        if (isF) {
-            QEPI(1, 0, em0, en0); QINIT_ASYNC(1, 0, kc);
-            CBAR();
-            if constexpr (RES) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + S0 + R0 + 2 * (S1 + R1)) : "memory");  // Q00's residual (L.P2)
-        }
-        CBAR();
-        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-        PHASE_BARRIER();
-        MFMA_Q(0, 0, fb0, gb0);
-        PHASE_BARRIER();
-        // ---- P2: Q01; reads B1; stage B0 of g+2; [last K-tile: Q00]
-        RD_B(fb1, gb1, st, 1);
-        STAGE_HALF(k2, v2, 2);
-        if (isL) { QEPI(0, 0, kc.m0, kc.n0); QINIT_ASYNC(0, 0, k1); }
-        if (isF) {
-            if constexpr (RES) { CBAR(); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + 2 * (S1 + R1)) : "memory"); }  // Q01 (L.P3)
-        }
-        CBAR();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        PHASE_BARRIER();
-        MFMA_Q(0, 1, fb1, gb1);
-        PHASE_BARRIER();
-        // ---- P3: Q11; reads A1; stage A0 of g+2; [last K-tile: Q01]
-        RD_A(st, 1);
-        STAGE_HALF(k2, v2, 0);
-        if (isL) { QEPI(0, 1, kc.m0, kc.n0); QINIT_ASYNC(0, 1, k1); }
-        if (isF) {
-            if constexpr (RES) { CBAR(); asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + S1 + R1) : "memory"); }    // Q11 (L.P4)
-        }
-        CBAR();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        PHASE_BARRIER();
-        MFMA_Q(1, 1, fb1, gb1);
-        PHASE_BARRIER();
-        // ---- P4: Q10 from registers; stage B1 and A1 of g+2; [last K-tile: Q11]; retire g+1
-        STAGE_HALF(k2, v2, 3);
-        STAGE_HALF(k2, v2, 1);
-        if (isL) {
-            QEPI(1, 1, kc.m0, kc.n0); QINIT_ASYNC(1, 1, k1);
-            CBAR();
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + 2 * (S0 + R0) + S1 + R1) : "memory");
-            em0 = kc.m0; en0 = kc.n0;
-        } else if (isF) {
-            // K-tile g+1, and (RES) Q10's residual from P1: 8 younger LDS-DMA
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(RES ? 8 : 8 + S1) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        }
-        PHASE_BARRIER();
-        MFMA_Q(1, 0, fb0, gb0);
-        PHASE_BARRIER();
-        kc = k1; k1 = k2;
-        {
-            const KT kn = kt_next(k2);
-            if (kn.k0 == 0 && kn.idx != k2.idx) v2 = vo_of(kn);
-            k2 = kn;
-        }
+    // The walk, tile by tile; K-tile kk of a tile restages its stage with K-tile kk + 2: of the
+    // same tile up to kk = nk - 3, of the next tile from the last two K-tiles.  Past the end of the
+    // walk the last K-tile is staged again (the same bytes into its own stage), so every wave
+    // issues the same VMEM operations on every K-tile and the counted waits hold.
+    const int kend = K * ESZ;
+    int st = 0;
+    for (int ti = 0; ti < my_tiles; ++ti) {
+        const bool last_tile = ti + 1 >= my_tiles;
+        int nm0 = cm0, nn0 = cn0;             // the next tile (the last one: itself)
+        if (!last_tile) tile_coords(slot + (ti + 1) * G, tiles_m, tiles_n, gm, nm0, nn0, 2 * BMH);
+        KTILE(ti > 0, false, v2, 2 * KTB, st);
+        for (int kb = 3 * KTB; kb < kend; kb += KTB) KTILE(false, false, v2, kb, st);
+        v2 = vo_of(nm0, nn0);
+        KTILE(false, false, v2, last_tile ? kend - KTB : 0, last_tile ? st ^ 1 : st);
+        KTILE(false, true, v2, last_tile ? kend - KTB : KTB, st);
+        cm0 = nm0; cn0 = nn0;
     }
     QEPI(1, 0, em0, en0);          // the last tile's Q10
     if (stagger && wr == 0) PHASE_BARRIER();
@@ -1272,6 +1288,8 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm256q(const u16* __restric
 #undef QINIT
 #undef QINIT_ASYNC
 #undef QEPI
+#undef LANE_RQ
+#undef KTILE
 #undef NBLK
 }
 
@@ -1585,19 +1603,36 @@ static int launch_gemm_skinny(void* stream, const void* A, int lda, const void* 
     return bf_check_launch();
 }
 
-// BF_GEMM_LOG=1: each distinct (shape, epilogue, kernel) choice of bf_gemm_bf16 once on stderr
-static void gemm_log(int M, int N, int K, int act, int resid, int resid_mod, int row_map, int c_bf16,
-                     const char* kern, int bm) {
+// BF_GEMM_LOG=1: each distinct (shape, epilogue, kernel) choice of bf_gemm_bf16 and bf_gemm_fp8 once
+// on stderr
+static bool gemm_log_on() {
     static const bool on = [] { const char* e = getenv("BF_GEMM_LOG"); return e && e[0] == '1'; }();
-    if (!on) return;
+    return on;
+}
+
+static void gemm_log_line(const char* line) {
     // never destroyed: no static destructor runs at process exit (exit order)
     static std::mutex& mu = *new std::mutex;
     static std::set<std::string>& seen = *new std::set<std::string>;
+    std::lock_guard<std::mutex> g(mu);
+    if (seen.insert(line).second) fprintf(stderr, "%s\n", line);
+}
+
+static void gemm_log(int M, int N, int K, int act, int resid, int resid_mod, int row_map, int c_bf16,
+                     const char* kern, int bm) {
+    if (!gemm_log_on()) return;
     char buf[256];
     snprintf(buf, sizeof buf, "bf_gemm M=%d N=%d K=%d act=%d resid=%d resid_mod=%d row_map=%d out=%s -> %s rows=%d",
              M, N, K, act, resid, resid_mod, row_map, c_bf16 ? "bf16" : "f32", kern, bm);
-    std::lock_guard<std::mutex> g(mu);
-    if (seen.insert(buf).second) fprintf(stderr, "%s\n", buf);
+    gemm_log_line(buf);
+}
+
+static void gemm_log_fp8(int M, int N, int K, int act, int resid, int out_kind, const char* kern, int bm) {
+    if (!gemm_log_on()) return;
+    char buf[256];
+    snprintf(buf, sizeof buf, "bf_gemm_fp8 M=%d N=%d K=%d act=%d resid=%d out=%s -> %s rows=%d", M, N, K, act, resid,
+             out_kind == 0 ? "f32" : out_kind == 1 ? "bf16" : "fp8", kern, bm);
+    gemm_log_line(buf);
 }
 
 // The product entry point: hand-written kernels only, chosen from the shape alone; the plan (NULL =
@@ -1750,6 +1785,7 @@ BF_API int bf_gemm_fp8_plan(const void* A, int lda, const void* W, int ldw, floa
         const int bm = 2 * (64 + 16 * mb1);
         const int tqm = (M + bm - 1) / bm;
         const int gq = gemm_grid((long long)tqm * t2n, cfg);
+        gemm_log_fp8(M, N, K, act, 0, out_kind, "k_gemm256q", bm);
         if (out_kind == 1) {
             if (act == 0) return launch_gemm256q<true, 0, false, 1>(mb1, cfg.group_m, gq, stream, A, lda, W, ldw, bias, nullptr, 0, C, ldc, M, N, K, t2n, tqm, scale, out_qscale);
             return launch_gemm256q<true, 1, false, 1>(mb1, cfg.group_m, gq, stream, A, lda, W, ldw, bias, nullptr, 0, C, ldc, M, N, K, t2n, tqm, scale, out_qscale);
@@ -1759,8 +1795,9 @@ BF_API int bf_gemm_fp8_plan(const void* A, int lda, const void* W, int ldw, floa
     }
 #define GEMM8(OB, AC, F8) launch_gemm256_f8<OB, AC, F8>(cfg.group_m, grid, bf_stream(stream), A, lda, W, ldw, scale, bias, \
                                                          resid, ldr, C, ldc, out_qscale, M, N, K, t2n, t2m)
+    if (out_kind == 0 && act != 0) return BF_ERR_UNSUPPORTED;   // (f32 GELU output: not on the path)
+    gemm_log_fp8(M, N, K, act, resid != nullptr, out_kind, "k_gemm256p", 256);
     if (out_kind == 0) {
-        if (act != 0) return BF_ERR_UNSUPPORTED;   // (f32 GELU output: not on the path)
         GEMM8(false, 0, 1);
     } else if (out_kind == 1) {
         if (act == 0) GEMM8(true, 0, 1);
