@@ -885,6 +885,69 @@ def png_workspace_bytes(F, H, W, total_file_bytes):
     return int(L.bf_png_workspace_bytes(F, H, W, total_file_bytes))
 
 
+ZLIB_STATUS = {8: "shorter than a zlib header + Adler-32", 16: "bad zlib / deflate stream", 32: "Adler-32 mismatch",
+               128: "inflated length is not 2 H W"}
+
+
+def zlib_decode_u16(streams, offsets, H, W, out=None, offsets_host=None, check=True, depth_scale=None, work=None):
+    """np.frombuffer(zlib.decompress(s), '<u2').reshape(H, W) for F bare zlib streams (the depth
+    frames of a ScanNet .sens container): streams u8 [total] device bytes of the streams back to
+    back at any byte offsets, offsets int64 [F+1] device (and the same offsets on the host,
+    `offsets_host`, to size the launch) -> out u16 [F,H,W] and the int32 status word per stream
+    (BF_PNG_* bits, ZLIB_STATUS).  depth_scale given: out f32 [F,H,W] = sample / depth_scale
+    (bf_zlib_decode_depth).  check=True synchronises and raises on any stream that did not decode."""
+    _need(streams, torch.uint8, "streams")
+    _need(offsets, torch.int64, "offsets")
+    if offsets_host is None:
+        offsets_host = offsets.cpu()
+    oh = [int(v) for v in offsets_host]
+    F_ = len(oh) - 1
+    if F_ < 0 or offsets.numel() != F_ + 1:
+        raise HipError("zlib_decode_u16: offsets [F+1]")
+    if oh[0] < 0 or any(oh[i + 1] < oh[i] for i in range(F_)):
+        raise HipError("zlib_decode_u16: offsets must not decrease")
+    total = oh[-1]
+    if total > streams.numel():
+        raise HipError("zlib_decode_u16: offsets run past the stream bytes")
+    mx = max((oh[i + 1] - oh[i] for i in range(F_)), default=0)
+    wb = zlib_workspace_bytes(F_, H, W, total)
+    if work is None or work.numel() < wb:
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=streams.device)
+    dt = torch.uint16 if depth_scale is None else torch.float32
+    if out is None:
+        out = torch.empty((F_, H, W), dtype=dt, device=streams.device)
+    _need(out, dt, "out")
+    if out.numel() != F_ * H * W:
+        raise HipError("zlib_decode_u16: out [F,H,W]")
+    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=streams.device)
+    if F_ == 0:
+        return out, status[:0]
+    if depth_scale is None:
+        rc = lib().bf_zlib_decode_u16(_ptr(streams), _ptr(offsets), c_int(F_), c_int(H), c_int(W),
+                                      ctypes.c_longlong(total), ctypes.c_longlong(mx), _ptr(out), _ptr(work),
+                                      c_size_t(wb), _ptr(status), _stream())
+    else:
+        rc = lib().bf_zlib_decode_depth(_ptr(streams), _ptr(offsets), c_int(F_), c_int(H), c_int(W),
+                                        ctypes.c_longlong(total), ctypes.c_longlong(mx), c_float(depth_scale),
+                                        _ptr(out), _ptr(work), c_size_t(wb), _ptr(status), _stream())
+    _check(rc, "bf_zlib_decode")
+    if check:
+        st = status.cpu()
+        bad = torch.nonzero(st).flatten().tolist()
+        if bad:
+            f = bad[0]
+            why = ", ".join(v for k, v in ZLIB_STATUS.items() if int(st[f]) & k)
+            raise HipError(f"zlib_decode_u16: {len(bad)} of {F_} streams did not decode (stream {f}: {why})")
+    return out, status
+
+
+def zlib_workspace_bytes(F, H, W, total_stream_bytes):
+    L = lib()
+    L.bf_zlib_workspace_bytes.restype = c_size_t
+    L.bf_zlib_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.c_longlong]
+    return int(L.bf_zlib_workspace_bytes(F, H, W, total_stream_bytes))
+
+
 def png_decode_rgb(files, offsets, H, W, out=None, offsets_host=None, check=True, work=None):
     """cv2.imread(color_path) + cvtColor(BGR2RGB) for F 8-bit PNGs (CA-1M's rgb/*.png,
     capture_stream.py:402): grey, RGB, grey + alpha or RGBA, non-interlaced (transparency is dropped,

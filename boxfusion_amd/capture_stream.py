@@ -10,6 +10,8 @@ colour + 16-bit depth frames and run the rest of the streams' per-frame work on 
 (bf_ingest_rgbd: cvtColor, cv2.resize, depth scaling, rotation); the 16-bit depth PNGs
 (bf_png_decode_u16), the baseline colour JPEGs (bf_jpeg_decode_rgb) and the 8-bit colour PNGs of
 CA-1M (bf_png_decode_rgb) are decoded on the GPU too, or on host threads (PIL) when configured so.
+A ScanNet scene still in its .sens container is read by boxfusion_amd.sens (its zlib depth
+frames: decode_depth_zlib, bf_zlib_decode_u16).
 """
 from __future__ import annotations
 
@@ -126,6 +128,16 @@ def decode_depth_pngs(blobs, H, W, device="cuda"):
     from boxfusion_amd import _lib
     files, offs, offs_h = upload_files(blobs, device)
     out, _ = _lib.png_decode_u16(files, offs, H, W, offsets_host=offs_h)
+    return out
+
+
+def decode_depth_zlib(blobs, H, W, device="cuda"):
+    """np.frombuffer(zlib.decompress(b), '<u2').reshape(H, W) for a batch of bare zlib streams (the
+    depth frames of a ScanNet .sens container, boxfusion_amd.sens), decoded on the GPU
+    (bf_zlib_decode_u16) -> u16 [F, H, W] on device; raises if any stream does not decode"""
+    from boxfusion_amd import _lib
+    streams, offs, offs_h = upload_files(blobs, device)
+    out, _ = _lib.zlib_decode_u16(streams, offs, H, W, offsets_host=offs_h)
     return out
 
 

@@ -1,0 +1,305 @@
+"""ScanNet `.sens` containers read directly: one file per scene holding the colour frames (baseline
+JPEG), the depth frames (bare zlib streams of little-endian uint16) and the camera -> world poses
+that the reference's ScannetDataset (capture_stream.py:119-311) reads from an exported
+color/*.jpg, depth/*.png, pose/*.txt tree.
+
+`SensFile` maps the file and indexes its frame records; `SensFrameStream` yields the sample dicts
+of `DecodedFrameStream` for the exported tree of the same scene, the colour frames through
+bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zlib on the host);
+`python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
+the header.
+
+Layout (little-endian, packed): uint32 version (4), uint64 n + n bytes sensor name, four row-major
+4x4 float32 matrices (colour intrinsics / extrinsics, depth intrinsics / extrinsics), int32 colour
+and depth compression, uint32 colour width, height, depth width, height, float32 depth_shift,
+uint64 frame count; per frame a 4x4 float32 camera -> world pose (all -inf when tracking was
+lost), uint64 colour and depth timestamps, uint64 colour and depth byte counts, the colour bytes,
+the depth bytes.
+"""
+from __future__ import annotations
+
+import mmap
+import os
+import struct
+import sys
+
+import numpy as np
+
+COLOR_COMPRESSION = {-1: "unknown", 0: "raw", 1: "png", 2: "jpeg"}
+DEPTH_COMPRESSION = {-1: "unknown", 0: "raw_ushort", 1: "zlib_ushort", 2: "occi_ushort"}
+_REC = struct.Struct("<16f4Q")           # pose, colour / depth timestamps, colour / depth sizes
+_TAIL = struct.Struct("<2i4IfQ")         # compressions, the four sizes, depth_shift, frame count
+
+
+class SensFile:
+    """a `.sens` file mapped read-only: header fields as attributes (`sensor_name`,
+    `intrinsic_color`, `extrinsic_color`, `intrinsic_depth`, `extrinsic_depth` [4,4] f32,
+    `color_compression`, `depth_compression`, `color_width`, `color_height`, `depth_width`,
+    `depth_height`, `depth_shift`, `num_frames`) and an index built by one walk over the frame
+    records: `color_index` / `depth_index` int64 [N,2] (byte offset, size), `timestamps` uint64
+    [N,2] (colour, depth), `poses` f32 [N,4,4] as written."""
+
+    def __init__(self, path):
+        self.path = os.fspath(path)
+        self._fh = open(self.path, "rb")
+        self._map = self._view = None
+        try:
+            size = os.fstat(self._fh.fileno()).st_size
+            if size == 0:
+                raise ValueError(f"{self.path}: empty file")
+            self._map = mmap.mmap(self._fh.fileno(), 0, access=mmap.ACCESS_READ)
+            self._view = memoryview(self._map)
+            self._parse(size)
+        except BaseException:
+            self.close()
+            raise
+
+    def _parse(self, size):
+        buf, path = self._map, self.path
+
+        def need(pos, n, what):
+            if pos + n > size:
+                raise ValueError(f"{path}: {what} runs past the end of the file ({pos} + {n} > {size} bytes)")
+
+        need(0, 12, "the file header")
+        version, nlen = struct.unpack_from("<IQ", buf, 0)
+        if version != 4:
+            raise ValueError(f"{path}: .sens version {version}, expected 4")
+        pos = 12
+        need(pos, nlen, "the sensor name")
+        self.sensor_name = bytes(buf[pos:pos + nlen]).decode("utf-8", "replace")
+        pos += nlen
+        need(pos, 4 * 64 + _TAIL.size, "the file header")
+        mats = np.frombuffer(buf, "<f4", 64, pos).reshape(4, 4, 4).astype(np.float32)
+        self.intrinsic_color, self.extrinsic_color, self.intrinsic_depth, self.extrinsic_depth = mats
+        pos += 4 * 64
+        (self.color_compression, self.depth_compression, self.color_width, self.color_height, self.depth_width,
+         self.depth_height, self.depth_shift, n) = _TAIL.unpack_from(buf, pos)
+        pos += _TAIL.size
+        if n * _REC.size > size - pos:
+            raise ValueError(f"{path}: {n} frames do not fit in the {size - pos} bytes after the header")
+        self.num_frames = n
+        self.color_index = np.zeros((n, 2), np.int64)
+        self.depth_index = np.zeros((n, 2), np.int64)
+        self.timestamps = np.zeros((n, 2), np.uint64)
+        self.poses = np.zeros((n, 4, 4), np.float32)
+        for i in range(n):
+            need(pos, _REC.size, f"the record of frame {i} (of {n})")
+            rec = _REC.unpack_from(buf, pos)
+            pos += _REC.size
+            self.poses[i] = np.asarray(rec[:16], np.float32).reshape(4, 4)
+            self.timestamps[i] = rec[16:18]
+            csz, dsz = rec[18], rec[19]
+            need(pos, csz, f"the colour data of frame {i}")
+            self.color_index[i] = (pos, csz)
+            pos += csz
+            need(pos, dsz, f"the depth data of frame {i}")
+            self.depth_index[i] = (pos, dsz)
+            pos += dsz
+
+    def __len__(self):
+        return self.num_frames
+
+    def color_bytes(self, i):
+        """frame i's colour data, a memoryview into the map (no copy; release it before close())"""
+        o, n = self.color_index[i]
+        return self._view[int(o):int(o + n)]
+
+    def depth_bytes(self, i):
+        """frame i's depth data, a memoryview into the map (no copy; release it before close())"""
+        o, n = self.depth_index[i]
+        return self._view[int(o):int(o + n)]
+
+    def poses_filled(self):
+        """the poses as the reference's load_poses keeps them (capture_stream.py:171-174): a pose
+        with any inf becomes the last valid pose before it; frames before the first valid pose
+        (the reference would hand out None there) get the first valid pose of the file"""
+        out = self.poses.copy()
+        bad = np.isinf(out).any(axis=(1, 2))
+        good = np.flatnonzero(~bad)
+        if len(good) == 0:
+            if len(out):
+                raise ValueError(f"{self.path}: no frame has a valid pose")
+            return out
+        last = out[good[0]]
+        for i in range(len(out)):
+            if bad[i]:
+                out[i] = last
+            else:
+                last = out[i]
+        return out
+
+    def depth_u16(self, i):
+        """frame i's depth decoded on the host -> u16 [depth_height, depth_width]"""
+        H, W = self.depth_height, self.depth_width
+        b = self.depth_bytes(i)
+        if self.depth_compression == 1:
+            import zlib
+            raw = zlib.decompress(b)
+        elif self.depth_compression == 0:
+            raw = b
+        else:
+            raise ValueError(f"{self.path}: depth compression "
+                             f"{DEPTH_COMPRESSION.get(self.depth_compression, self.depth_compression)} is not supported")
+        if len(raw) != 2 * H * W:
+            raise ValueError(f"{self.path}: depth frame {i} holds {len(raw)} bytes, expected {2 * H * W}")
+        return np.frombuffer(raw, "<u2").reshape(H, W)
+
+    def close(self):
+        if self._view is not None:
+            self._view.release()
+            self._view = None
+        if self._map is not None:
+            self._map.close()
+            self._map = None
+        if self._fh is not None:
+            self._fh.close()
+            self._fh = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class SensFrameStream:
+    """a `.sens` file as demo.py's dataset: the samples DecodedFrameStream yields for the exported
+    tree of the same scene, without the tree.  Per batch of `batch` frames the colour JPEGs are
+    decoded by bf_jpeg_decode_rgb (color_decode="host": PIL) and the zlib depth streams by
+    bf_zlib_decode_u16 (depth_decode="host": zlib.decompress); raw-ushort depth is uploaded as it
+    is.  K defaults to the depth intrinsics (the colour image is resized to the depth size, as the
+    reference's cv2.resize(color, (W, H)) does), depth_scale to the file's depth_shift; poses are
+    `poses_filled()`; frames start, start + step, ... below stop, `timestamp` = the frame's index
+    in the file."""
+
+    def __init__(self, sens, K=None, depth_scale=None, device="cuda", video_id=0, batch=16, start=0, stop=None,
+                 step=1, color_decode="gpu", depth_decode="gpu"):
+        self.sens = sens if isinstance(sens, SensFile) else SensFile(sens)
+        s = self.sens
+        if s.color_compression != 2:
+            raise ValueError(f"{s.path}: colour compression {COLOR_COMPRESSION.get(s.color_compression, s.color_compression)}"
+                             " is not supported (jpeg only)")
+        if s.depth_compression not in (0, 1):
+            raise ValueError(f"{s.path}: depth compression {DEPTH_COMPRESSION.get(s.depth_compression, s.depth_compression)}"
+                             " is not supported (zlib_ushort or raw_ushort)")
+        if depth_decode not in ("gpu", "host"):
+            raise ValueError("depth_decode: 'gpu' or 'host'")
+        if color_decode not in ("gpu", "host"):
+            raise ValueError("color_decode: 'gpu' or 'host'")
+        self.K = np.asarray(s.intrinsic_depth[:3, :3] if K is None else K, np.float32)
+        self.scale = float(s.depth_shift if depth_scale is None else depth_scale)
+        self.dev, self.video_id, self.batch = device, video_id, max(1, int(batch))
+        self.frames = range(s.num_frames)[start:stop:step]
+        self.color_decode, self.depth_decode = color_decode, depth_decode
+        self.poses = s.poses_filled()
+
+    def __len__(self):
+        return len(self.frames)
+
+    def _depths(self, idx):
+        import torch
+        from boxfusion_amd.capture_stream import decode_depth_zlib
+        s = self.sens
+        H, W = s.depth_height, s.depth_width
+        if s.depth_compression == 1 and self.depth_decode == "gpu":
+            return decode_depth_zlib([s.depth_bytes(i) for i in idx], H, W, self.dev)
+        arr = np.stack([s.depth_u16(i) for i in idx])
+        return torch.from_numpy(arr.view(np.int16)).to(self.dev).view(torch.uint16)
+
+    def _colors(self, idx):
+        import torch
+        from boxfusion_amd.capture_stream import decode_color_jpegs
+        s = self.sens
+        if self.color_decode == "gpu":
+            return decode_color_jpegs([s.color_bytes(i) for i in idx], s.color_height, s.color_width, self.dev)
+        import io
+        from PIL import Image
+        out = []
+        for i in idx:
+            rgb = np.array(Image.open(io.BytesIO(s.color_bytes(i))).convert("RGB"))
+            out.append(torch.from_numpy(rgb).to(self.dev, non_blocking=True))
+        return out
+
+    def __iter__(self):
+        import torch
+        from boxfusion_amd.capture_stream import make_sample_decoded
+        for b0 in range(0, len(self.frames), self.batch):
+            idx = list(self.frames[b0:b0 + self.batch])
+            deps, cols = self._depths(idx), self._colors(idx)
+            for j, i in enumerate(idx):
+                yield make_sample_decoded(cols[j], deps[j].view(torch.int16), self.scale, self.K, self.poses[i],
+                                          video_id=self.video_id, index=i, src_bgr=False)
+
+
+def _matrix_text(m):
+    return "".join(" ".join(repr(float(v)) for v in row) + "\n" for row in np.asarray(m, np.float32))
+
+
+def export(sens, out_dir, start=0, stop=None, step=1):
+    """write the reference's tree for the frames start, start + step, ... below stop:
+    color/<i>.jpg (the container's bytes), depth/<i>.png (16-bit grey), pose/<i>.txt (the pose as
+    written, -inf included) and intrinsic/intrinsic_{color,depth}.txt; returns the frame indices"""
+    from PIL import Image
+    if sens.color_compression != 2:
+        raise ValueError(f"{sens.path}: colour compression "
+                         f"{COLOR_COMPRESSION.get(sens.color_compression, sens.color_compression)} is not supported (jpeg only)")
+    for d in ("color", "depth", "pose", "intrinsic"):
+        os.makedirs(os.path.join(out_dir, d), exist_ok=True)
+    for name in ("intrinsic_color", "intrinsic_depth"):
+        with open(os.path.join(out_dir, "intrinsic", name + ".txt"), "w") as fh:
+            fh.write(_matrix_text(getattr(sens, name)))
+    frames = list(range(sens.num_frames)[start:stop:step])
+    for i in frames:
+        with open(os.path.join(out_dir, "color", f"{i}.jpg"), "wb") as fh:
+            fh.write(sens.color_bytes(i))
+        Image.fromarray(np.ascontiguousarray(sens.depth_u16(i)).astype(np.uint16)).save(
+            os.path.join(out_dir, "depth", f"{i}.png"))
+        with open(os.path.join(out_dir, "pose", f"{i}.txt"), "w") as fh:
+            fh.write(_matrix_text(sens.poses[i]))
+    return frames
+
+
+def info(sens, out=None):
+    out = sys.stdout if out is None else out
+    print(f"{sens.path}: version 4, sensor {sens.sensor_name!r}", file=out)
+    print(f"frames       {sens.num_frames}", file=out)
+    print(f"colour       {sens.color_width} x {sens.color_height}, "
+          f"{COLOR_COMPRESSION.get(sens.color_compression, sens.color_compression)}", file=out)
+    print(f"depth        {sens.depth_width} x {sens.depth_height}, "
+          f"{DEPTH_COMPRESSION.get(sens.depth_compression, sens.depth_compression)}, depth_shift {sens.depth_shift:g}",
+          file=out)
+    for name in ("intrinsic_color", "extrinsic_color", "intrinsic_depth", "extrinsic_depth"):
+        print(name, file=out)
+        out.write(_matrix_text(getattr(sens, name)))
+    if sens.num_frames:
+        lost = int(np.isinf(sens.poses).any(axis=(1, 2)).sum())
+        print(f"poses        {lost} of {sens.num_frames} without tracking (-inf)", file=out)
+        print(f"data         colour {int(sens.color_index[:, 1].sum())} bytes, depth {int(sens.depth_index[:, 1].sum())} bytes",
+              file=out)
+
+
+def main(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m boxfusion_amd.sens", description="ScanNet .sens containers")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    pi = sub.add_parser("info", help="print the header fields")
+    pi.add_argument("sens")
+    pe = sub.add_parser("export", help="write the color/ depth/ pose/ intrinsic/ tree")
+    pe.add_argument("sens")
+    pe.add_argument("out")
+    pe.add_argument("--start", type=int, default=0)
+    pe.add_argument("--stop", type=int, default=None)
+    pe.add_argument("--step", type=int, default=1)
+    a = p.parse_args(argv)
+    with SensFile(a.sens) as s:
+        if a.cmd == "info":
+            info(s)
+        else:
+            frames = export(s, a.out, a.start, a.stop, a.step)
+            print(f"{len(frames)} frames -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -676,6 +676,30 @@ int bf_png_decode_rgb(const uint8_t* files, const int64_t* offsets, int F, int H
                       long long total_file_bytes, long long max_file_bytes, uint8_t* rgb,
                       void* work, size_t work_bytes, int32_t* status, void* stream);
 
+/* ---- bare zlib depth streams (the depth frames inside a ScanNet .sens container, depth compression
+ * zlib_ushort; exported to depth/<i>.png they are what capture_stream.py:197 reads) ----
+ * F zlib streams (RFC 1950), back to back in device memory: stream f = streams[offsets[f] ..
+ * offsets[f+1]) at any byte alignment (offsets int64 [F+1], device; total_stream_bytes = offsets[F],
+ * max_stream_bytes = the longest stream, both as the host uploaded them), each inflating to exactly
+ * 2 H W bytes, the H x W samples row-major and little-endian with no filter bytes -> out u16 [F,H,W].
+ * status int32 [F] (device) gets, per stream that did not decode (its out samples are then undefined,
+ * no other stream's are touched), the BF_PNG_* bits of the same meaning:
+ *   BF_PNG_BAD_CHUNK  shorter than the 2 header bytes + the 4 bytes of Adler-32, or longer than max_stream_bytes
+ *   BF_PNG_BAD_ZLIB   bad CMF / FLG, preset dictionary, invalid block / code / distance
+ *   BF_PNG_BAD_ADLER  Adler-32 mismatch
+ *   BF_PNG_SIZE       inflated length != 2 H W (shorter or longer; nothing is written past H W samples)
+ * W <= 4096, 2 H W < 2^31 and a stream under 2 GiB, else BF_ERR_UNSUPPORTED.  work:
+ * bf_zlib_workspace_bytes(F, H, W, total_stream_bytes) bytes, caller-owned device memory. */
+size_t bf_zlib_workspace_bytes(int F, int H, int W, long long total_stream_bytes);
+int bf_zlib_decode_u16(const uint8_t* streams, const int64_t* offsets, int F, int H, int W,
+                       long long total_stream_bytes, long long max_stream_bytes, uint16_t* out, void* work,
+                       size_t work_bytes, int32_t* status, void* stream);
+/* the same decode with the streams' depth scaling: depth_out f32 [F,H,W] = sample / depth_scale
+ * (IEEE f32 division, as bf_png_decode_depth) */
+int bf_zlib_decode_depth(const uint8_t* streams, const int64_t* offsets, int F, int H, int W,
+                         long long total_stream_bytes, long long max_stream_bytes, float depth_scale,
+                         float* depth_out, void* work, size_t work_bytes, int32_t* status, void* stream);
+
 /* ---- colour JPEG decode (reference: cv2.imread(color_path), capture_stream.py:194 ScanNet /
  * :402 CA-1M -- libjpeg's default decompression, which PIL's decoder reproduces) ----
  * F baseline (sequential Huffman, 8-bit) JPEG files, back to back in device memory as for the PNG
