@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes
+import functools
 import threading
 import weakref
 import sys
@@ -82,6 +83,10 @@ def lib():
         _LIB.bf_obb_iou_workspace_size.argtypes = [c_int]
         _LIB.bf_depth_standardize_workspace_size.restype = c_size_t
         _LIB.bf_depth_standardize_workspace_size.argtypes = [c_int, c_int, c_int]
+        for f in (_LIB.bf_png_workspace_bytes, _LIB.bf_zlib_workspace_bytes, _LIB.bf_png_rgb_workspace_bytes):
+            f.restype, f.argtypes = c_size_t, [c_int, c_int, c_int, ctypes.c_longlong]
+        _LIB.bf_jpeg_workspace_bytes.restype = c_size_t
+        _LIB.bf_jpeg_workspace_bytes.argtypes = [c_int, c_int, c_int]
     return _LIB
 
 
@@ -131,6 +136,22 @@ def _need(t, dtype, name):
     return t
 
 
+def _timed(work):
+    """decorator of a wrapper that KernelTimer records: while a timer entered on this thread is
+    active, work(*args, **kwargs) -> (tags, flops, bytes) of the call and the call runs between the
+    timer's two events; otherwise the call goes straight through.  `work` declares the wrapper's
+    own signature, so a parameter added to one and not the other raises instead of shifting."""
+    def deco(fn):
+        @functools.wraps(fn)
+        def timed(*args, **kwargs):
+            t = _timer()
+            if t is None:
+                return fn(*args, **kwargs)
+            return t.record(*work(*args, **kwargs), lambda: fn(*args, **kwargs))
+        return timed
+    return deco
+
+
 def version():
     return lib().bf_version().decode()
 
@@ -164,6 +185,13 @@ def project_boxes(corners, cam_pose, K, W, H):
     return uv
 
 
+def _obb_iou_work(corners):
+    n = int(corners.shape[0])
+    # work = box pairs (i < j) of the IoU matrix (gate + 25^3 grid count launches)
+    return dict(kind="obb_iou", n=n), n * (n - 1) / 2.0, 96.0 * n + 8.0 * n * n
+
+
+@_timed(_obb_iou_work)
 def obb_iou_matrix(corners):
     corners = _need(corners.contiguous(), torch.float32, "corners")
     n = corners.shape[0]
@@ -251,6 +279,12 @@ def rows_gather(pairs, idx=None, n_out=None, outs=None, status=None):
 # ------------------------------------------------------------------------------------------
 # association
 # ------------------------------------------------------------------------------------------
+def _nms_scan_work(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_num, cfg, out=None):
+    n = int(scores.shape[0])
+    return dict(kind="nms_scan", n=n), float(n), 8.0 * n * n
+
+
+@_timed(_nms_scan_work)
 def nms_scan(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_num, cfg: NmsCfg,
              out=None):
     """returns device tensors: keep, succ, events, counts (n_keep, n_success, n_events, status);
@@ -340,11 +374,21 @@ def fusion_fit(view_off, n_views, view_box, view_R, view_score, view_pose, view_
     L.bf_fusion_fit_workspace_size.restype = ctypes.c_size_t
     nbytes = L.bf_fusion_fit_workspace_size(c_int(n_jobs), c_int(max_views), c_int(cfg.pst_size))
     ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-    _check(L.bf_fusion_fit(_ptr(view_off), _ptr(n_views), c_int(n_jobs), c_int(max_views),
-                           _ptr(view_box), _ptr(view_R), _ptr(view_score), _ptr(view_pose),
-                           _ptr(view_tc), _ptr(pst), ctypes.byref(cfg), _ptr(out_box),
-                           _ptr(out_upd), _ptr(out_it), _ptr(tr), _ptr(status), _ptr(ws),
-                           _stream()), "bf_fusion_fit")
+    launch = lambda: _check(L.bf_fusion_fit(_ptr(view_off), _ptr(n_views), c_int(n_jobs), c_int(max_views),
+                                            _ptr(view_box), _ptr(view_R), _ptr(view_score), _ptr(view_pose),
+                                            _ptr(view_tc), _ptr(pst), ctypes.byref(cfg), _ptr(out_box),
+                                            _ptr(out_upd), _ptr(out_it), _ptr(tr), _ptr(status), _ptr(ws),
+                                            _stream()), "bf_fusion_fit")
+    # KernelTimer, by hand (not _timed): the work is known only from what this launch writes
+    t = _timer()
+    if t is None:
+        launch()
+    else:
+        P = int(cfg.pst_size)
+        # work = particle-view fitness evaluations: sum over jobs of views * particles * iterations
+        # (the iteration counts are read when the summary is taken)
+        t.record(dict(kind="fusion_fit", jobs=n_jobs),
+                 lambda: float((out_it.long() * n_views.long()).sum().item() * P), 0.0, launch)
     if packed_out:
         return out_box, packed, tr
     return out_box, out_upd, out_it, status, tr
@@ -515,9 +559,9 @@ def depth_workspace(b, h, w, device):
     return ws
 
 
-def depth_standardize(depth, out=None, params=None):
+def depth_standardize(depth, out=None, params=None, ws=None):
     """depth f32[b,h,w] -> (standardised f32[b,h,w], params f32[b,2])"""
-    return depth_preprocess(depth, out=out, params=params)
+    return depth_preprocess(depth, out=out, params=params, ws=ws)
 
 
 def depth_preprocess(depth, K=None, RT=None, max_depth=10.0, out=None, params=None, xyz=None, valid=None,
@@ -545,11 +589,21 @@ def depth_preprocess(depth, K=None, RT=None, max_depth=10.0, out=None, params=No
             raise HipError("bf_depth_preprocess under graph capture needs a caller-owned ws "
                            "(new_depth_workspace): the per-stream cached workspace is shared")
         ws = depth_workspace(b, h, w, depth.device)
-    _check(lib().bf_depth_preprocess(_ptr(depth), c_int(b), c_int(h), c_int(w), _ptr(out), _ptr(params),
-                                     _ptr(K) if bp else None, _ptr(RT) if bp else None,
-                                     c_float(max_depth if max_depth is not None else 0.0),
-                                     _ptr(xyz) if bp else None, _ptr(valid) if bp else None, _ptr(ws),
-                                     _stream()), "bf_depth_preprocess")
+    launch = lambda: _check(lib().bf_depth_preprocess(
+        _ptr(depth), c_int(b), c_int(h), c_int(w), _ptr(out), _ptr(params), _ptr(K) if bp else None,
+        _ptr(RT) if bp else None, c_float(max_depth if max_depth is not None else 0.0),
+        _ptr(xyz) if bp else None, _ptr(valid) if bp else None, _ptr(ws), _stream()), "bf_depth_preprocess")
+    # KernelTimer, by hand (not _timed): the outputs and the workspace above are allocated before
+    # the start event, so the events bracket the launches only
+    t = _timer()
+    if t is None:
+        launch()
+    else:
+        n = float(b * h * w)
+        # algorithmic bytes: read the depth once, write the standardised map (+ xyz and
+        # the valid mask when back-projecting)
+        t.record(dict(kind="depth", backproject=bp, b=b, h=h, w=w), 0.0, 8.0 * n + (13.0 * n if bp else 0.0),
+                 launch)
     if bp:
         return out, params, xyz, valid.view(torch.bool)
     return out, params
@@ -635,6 +689,20 @@ def gemm_grid(M, N, K, plan=None):
     return r
 
 
+def _gemm_work(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype=torch.bfloat16,
+               row_map=None, m=None, plan=None):
+    M = a.shape[0] if m is None else m
+    N, K = w.shape
+    ob = (out.dtype if out is not None else out_dtype) == torch.bfloat16
+    tags = dict(kind="gemm", act=ACT[act], out_bf16=ob, resid=resid is not None, M=M, N=N, K=K,
+                large=bool(lib().bf_gemm_large_tiles(c_int(M), c_int(N), c_int(K))))
+    nbytes = 2.0 * (M * K + N * K) + M * N * (2 if ob else 4)
+    if resid is not None:
+        nbytes += 4.0 * (M * N if not resid_mod else resid_mod * N)
+    return tags, 2.0 * M * N * K, nbytes
+
+
+@_timed(_gemm_work)
 def gemm(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype=torch.bfloat16,
          row_map=None, m=None, plan=None):
     """out[orow(r)] = resid[...] + act(a @ w.T + bias); a bf16 [M,K] (row stride a.stride(0)),
@@ -665,6 +733,14 @@ def gemm(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype
     return out
 
 
+def _attention_work(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs=None, k_bs=None, v_bs=None,
+                    o_bs=None, o_map=None, variant=0):
+    bh = float(batch * heads)
+    return (dict(kind="attn", D=head_dim, sq=sq, sk=sk, batch=batch, heads=heads),
+            4.0 * bh * sq * sk * head_dim, 2.0 * bh * head_dim * (2 * sq + 2 * sk))
+
+
+@_timed(_attention_work)
 def attention(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs=None, k_bs=None, v_bs=None,
               o_bs=None, o_map=None, variant=0):
     """q/k/v/o are 2-D token-major views [batch*S, >= heads*head_dim] (any row stride).
@@ -692,6 +768,14 @@ def attention(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs=None, k_bs
     return o
 
 
+def _attention_fp8out_work(q, k, v, o, batch, heads, sq, sk, head_dim, scale, out_qscale, q_bs=None,
+                           k_bs=None, v_bs=None, o_bs=None, variant=0):
+    bh = float(batch * heads)
+    return (dict(kind="attn", D=head_dim, sq=sq, sk=sk, batch=batch, heads=heads, fp8out=True),
+            4.0 * bh * sq * sk * head_dim, bh * head_dim * (2 * sq + 4 * sk + sq))
+
+
+@_timed(_attention_fp8out_work)
 def attention_fp8out(q, k, v, o, batch, heads, sq, sk, head_dim, scale, out_qscale, q_bs=None,
                      k_bs=None, v_bs=None, o_bs=None, variant=0):
     """attention() with an fp8 e4m3 output o = saturate(softmax(q k^T) v * out_qscale)"""
@@ -830,6 +914,53 @@ PNG_STATUS = {1: "bad signature", 2: "bad IHDR", 4: "unsupported PNG kind", 8: "
               16: "bad zlib / deflate stream", 32: "Adler-32 mismatch", 64: "bad row filter", 128: "size mismatch"}
 
 
+def _decode_batch(name, entry, workspace_bytes, status_bits, noun, data, offsets, H, W, tail, dtype, out,
+                  offsets_host, check, work, extra=(), sized=True):
+    """the one front end of the batched decoders (png_decode_u16 / zlib_decode_u16 / png_decode_rgb /
+    jpeg_decode_rgb, whose docstrings give the arguments): `data` u8 [total] holds F `noun`s back to
+    back at `offsets` -> (out `dtype` [F,H,W,*tail], int32 status [F]); a status word's set bits read
+    as `status_bits`.  Every host check runs before anything touches the device.  sized: `entry` and
+    `workspace_bytes` take the total and the largest member's byte counts, which need the host
+    offsets (read back when not given); otherwise host offsets are only validated when given.
+    extra: C arguments that go between the sizes and `out`."""
+    _need(data, torch.uint8, f"{name}: {noun}s")
+    _need(offsets, torch.int64, f"{name}: offsets")
+    F_ = offsets.numel() - 1
+    if offsets_host is None and sized:
+        offsets_host = offsets.cpu()
+    oh = None if offsets_host is None else [int(v) for v in offsets_host]
+    if F_ < 0 or (oh is not None and len(oh) != F_ + 1):
+        raise HipError(f"{name}: offsets [F+1]")
+    if oh is not None:
+        member = [oh[i + 1] - oh[i] for i in range(F_)]
+        if oh[0] < 0 or min(member, default=0) < 0:
+            raise HipError(f"{name}: offsets must not decrease")
+        if oh[-1] > data.numel():
+            raise HipError(f"{name}: offsets run past the {noun} bytes")
+    if out is None:
+        out = torch.empty((F_, H, W, *tail), dtype=dtype, device=data.device)
+    _need(out, dtype, f"{name}: out")
+    if out.numel() != F_ * H * W * int(np.prod(tail)):
+        raise HipError(f"{name}: out [{','.join(['F', 'H', 'W', *map(str, tail)])}]")
+    status = torch.zeros(F_, dtype=torch.int32, device=data.device)
+    if F_ == 0:
+        return out, status
+    sizes = (oh[-1], max(member)) if sized else ()
+    wb = workspace_bytes(F_, H, W, *sizes[:1])
+    if work is None or work.numel() < wb:
+        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=data.device)
+    _check(entry(_ptr(data), _ptr(offsets), c_int(F_), c_int(H), c_int(W), *map(ctypes.c_longlong, sizes), *extra,
+                 _ptr(out), _ptr(work), c_size_t(wb), _ptr(status), _stream()), entry.__name__)
+    if check:
+        st = status.cpu()
+        bad = torch.nonzero(st).flatten().tolist()
+        if bad:
+            f = bad[0]
+            why = ", ".join(v for k, v in status_bits.items() if int(st[f]) & k)
+            raise HipError(f"{name}: {len(bad)} of {F_} {noun}s did not decode ({noun} {f}: {why})")
+    return out, status
+
+
 def png_decode_u16(files, offsets, H, W, out=None, offsets_host=None, check=True, depth_scale=None, work=None):
     """cv2.imread(path, IMREAD_UNCHANGED) for F 16-bit greyscale PNGs (capture_stream.py:197/:405):
     files u8 [total] device bytes of the files back to back, offsets int64 [F+1] device (and the
@@ -837,52 +968,15 @@ def png_decode_u16(files, offsets, H, W, out=None, offsets_host=None, check=True
     status word per file.  depth_scale given: out f32 [F,H,W] = sample / depth_scale
     (capture_stream.py:203, bf_png_decode_depth).  check=True synchronises and raises on any file
     that did not decode."""
-    _need(files, torch.uint8, "files")
-    _need(offsets, torch.int64, "offsets")
-    if offsets_host is None:
-        offsets_host = offsets.cpu()
-    oh = [int(v) for v in offsets_host]
-    F_ = len(oh) - 1
-    if F_ < 0 or offsets.numel() != F_ + 1:
-        raise HipError("png_decode_u16: offsets [F+1]")
-    total = oh[-1] if F_ >= 0 else 0
-    if total > files.numel():
-        raise HipError("png_decode_u16: offsets run past the file bytes")
-    mx = max((oh[i + 1] - oh[i] for i in range(F_)), default=0)
-    wb = png_workspace_bytes(F_, H, W, total)
-    if work is None or work.numel() < wb:
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=files.device)
-    dt = torch.uint16 if depth_scale is None else torch.float32
-    if out is None:
-        out = torch.empty((F_, H, W), dtype=dt, device=files.device)
-    _need(out, dt, "out")
-    if out.numel() != F_ * H * W:
-        raise HipError("png_decode_u16: out [F,H,W]")
-    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=files.device)
-    if depth_scale is None:
-        rc = lib().bf_png_decode_u16(_ptr(files), _ptr(offsets), c_int(F_), c_int(H), c_int(W), ctypes.c_longlong(total),
-                                     ctypes.c_longlong(mx), _ptr(out), _ptr(work), c_size_t(wb), _ptr(status),
-                                     _stream())
-    else:
-        rc = lib().bf_png_decode_depth(_ptr(files), _ptr(offsets), c_int(F_), c_int(H), c_int(W),
-                                       ctypes.c_longlong(total), ctypes.c_longlong(mx), c_float(depth_scale),
-                                       _ptr(out), _ptr(work), c_size_t(wb), _ptr(status), _stream())
-    _check(rc, "bf_png_decode")
-    if check and F_:
-        st = status[:F_].cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            f = bad[0]
-            why = ", ".join(v for k, v in PNG_STATUS.items() if int(st[f]) & k)
-            raise HipError(f"png_decode_u16: {len(bad)} of {F_} files did not decode (file {f}: {why})")
-    return out, status[:F_]
+    L = lib()
+    entry, dt, extra = ((L.bf_png_decode_u16, torch.uint16, ()) if depth_scale is None else
+                        (L.bf_png_decode_depth, torch.float32, (c_float(depth_scale),)))
+    return _decode_batch("png_decode_u16", entry, png_workspace_bytes, PNG_STATUS, "file", files, offsets, H, W, (),
+                         dt, out, offsets_host, check, work, extra)
 
 
 def png_workspace_bytes(F, H, W, total_file_bytes):
-    L = lib()
-    L.bf_png_workspace_bytes.restype = c_size_t
-    L.bf_png_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.c_longlong]
-    return int(L.bf_png_workspace_bytes(F, H, W, total_file_bytes))
+    return int(lib().bf_png_workspace_bytes(F, H, W, total_file_bytes))
 
 
 ZLIB_STATUS = {8: "shorter than a zlib header + Adler-32", 16: "bad zlib / deflate stream", 32: "Adler-32 mismatch",
@@ -896,56 +990,15 @@ def zlib_decode_u16(streams, offsets, H, W, out=None, offsets_host=None, check=T
     `offsets_host`, to size the launch) -> out u16 [F,H,W] and the int32 status word per stream
     (BF_PNG_* bits, ZLIB_STATUS).  depth_scale given: out f32 [F,H,W] = sample / depth_scale
     (bf_zlib_decode_depth).  check=True synchronises and raises on any stream that did not decode."""
-    _need(streams, torch.uint8, "streams")
-    _need(offsets, torch.int64, "offsets")
-    if offsets_host is None:
-        offsets_host = offsets.cpu()
-    oh = [int(v) for v in offsets_host]
-    F_ = len(oh) - 1
-    if F_ < 0 or offsets.numel() != F_ + 1:
-        raise HipError("zlib_decode_u16: offsets [F+1]")
-    if oh[0] < 0 or any(oh[i + 1] < oh[i] for i in range(F_)):
-        raise HipError("zlib_decode_u16: offsets must not decrease")
-    total = oh[-1]
-    if total > streams.numel():
-        raise HipError("zlib_decode_u16: offsets run past the stream bytes")
-    mx = max((oh[i + 1] - oh[i] for i in range(F_)), default=0)
-    wb = zlib_workspace_bytes(F_, H, W, total)
-    if work is None or work.numel() < wb:
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=streams.device)
-    dt = torch.uint16 if depth_scale is None else torch.float32
-    if out is None:
-        out = torch.empty((F_, H, W), dtype=dt, device=streams.device)
-    _need(out, dt, "out")
-    if out.numel() != F_ * H * W:
-        raise HipError("zlib_decode_u16: out [F,H,W]")
-    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=streams.device)
-    if F_ == 0:
-        return out, status[:0]
-    if depth_scale is None:
-        rc = lib().bf_zlib_decode_u16(_ptr(streams), _ptr(offsets), c_int(F_), c_int(H), c_int(W),
-                                      ctypes.c_longlong(total), ctypes.c_longlong(mx), _ptr(out), _ptr(work),
-                                      c_size_t(wb), _ptr(status), _stream())
-    else:
-        rc = lib().bf_zlib_decode_depth(_ptr(streams), _ptr(offsets), c_int(F_), c_int(H), c_int(W),
-                                        ctypes.c_longlong(total), ctypes.c_longlong(mx), c_float(depth_scale),
-                                        _ptr(out), _ptr(work), c_size_t(wb), _ptr(status), _stream())
-    _check(rc, "bf_zlib_decode")
-    if check:
-        st = status.cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            f = bad[0]
-            why = ", ".join(v for k, v in ZLIB_STATUS.items() if int(st[f]) & k)
-            raise HipError(f"zlib_decode_u16: {len(bad)} of {F_} streams did not decode (stream {f}: {why})")
-    return out, status
+    L = lib()
+    entry, dt, extra = ((L.bf_zlib_decode_u16, torch.uint16, ()) if depth_scale is None else
+                        (L.bf_zlib_decode_depth, torch.float32, (c_float(depth_scale),)))
+    return _decode_batch("zlib_decode_u16", entry, zlib_workspace_bytes, ZLIB_STATUS, "stream", streams, offsets, H, W,
+                         (), dt, out, offsets_host, check, work, extra)
 
 
 def zlib_workspace_bytes(F, H, W, total_stream_bytes):
-    L = lib()
-    L.bf_zlib_workspace_bytes.restype = c_size_t
-    L.bf_zlib_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.c_longlong]
-    return int(L.bf_zlib_workspace_bytes(F, H, W, total_stream_bytes))
+    return int(lib().bf_zlib_workspace_bytes(F, H, W, total_stream_bytes))
 
 
 def png_decode_rgb(files, offsets, H, W, out=None, offsets_host=None, check=True, work=None):
@@ -954,87 +1007,31 @@ def png_decode_rgb(files, offsets, H, W, out=None, offsets_host=None, check=True
     not composited, as cv2's default flag does); files / offsets / offsets_host as png_decode_u16
     -> out u8 [F,H,W,3] in RGB order and the int32 status word per file (BF_PNG_* bits).  A batch may
     mix the four kinds.  check=True synchronises and raises on any file that did not decode."""
-    _need(files, torch.uint8, "files")
-    _need(offsets, torch.int64, "offsets")
-    if offsets_host is None:
-        offsets_host = offsets.cpu()
-    oh = [int(v) for v in offsets_host]
-    F_ = len(oh) - 1
-    if F_ < 0 or offsets.numel() != F_ + 1:
-        raise HipError("png_decode_rgb: offsets [F+1]")
-    total = oh[-1]
-    if total > files.numel():
-        raise HipError("png_decode_rgb: offsets run past the file bytes")
-    mx = max((oh[i + 1] - oh[i] for i in range(F_)), default=0)
-    wb = png_rgb_workspace_bytes(F_, H, W, total)
-    if work is None or work.numel() < wb:
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=files.device)
-    if out is None:
-        out = torch.empty((F_, H, W, 3), dtype=torch.uint8, device=files.device)
-    _need(out, torch.uint8, "out")
-    if out.numel() != F_ * H * W * 3:
-        raise HipError("png_decode_rgb: out [F,H,W,3]")
-    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=files.device)
-    _check(lib().bf_png_decode_rgb(_ptr(files), _ptr(offsets), c_int(F_), c_int(H), c_int(W), ctypes.c_longlong(total),
-                                   ctypes.c_longlong(mx), _ptr(out), _ptr(work), c_size_t(wb), _ptr(status),
-                                   _stream()), "bf_png_decode_rgb")
-    if check and F_:
-        st = status[:F_].cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            f = bad[0]
-            why = ", ".join(v for k, v in PNG_STATUS.items() if int(st[f]) & k)
-            raise HipError(f"png_decode_rgb: {len(bad)} of {F_} files did not decode (file {f}: {why})")
-    return out, status[:F_]
+    return _decode_batch("png_decode_rgb", lib().bf_png_decode_rgb, png_rgb_workspace_bytes, PNG_STATUS, "file", files,
+                         offsets, H, W, (3,), torch.uint8, out, offsets_host, check, work)
 
 
 def png_rgb_workspace_bytes(F, H, W, total_file_bytes):
-    L = lib()
-    L.bf_png_rgb_workspace_bytes.restype = c_size_t
-    L.bf_png_rgb_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.c_longlong]
-    return int(L.bf_png_rgb_workspace_bytes(F, H, W, total_file_bytes))
+    return int(lib().bf_png_rgb_workspace_bytes(F, H, W, total_file_bytes))
 
 
 JPEG_STATUS = {1: "bad / missing marker segment", 2: "unsupported JPEG kind (not baseline 1/3-component h2v2/h2v1/h1v1)",
                4: "size mismatch", 8: "corrupt entropy-coded data"}
 
 
-def jpeg_decode_rgb(files, offsets, H, W, out=None, check=True, work=None):
+def jpeg_decode_rgb(files, offsets, H, W, out=None, check=True, work=None, offsets_host=None):
     """cv2.imread(color_path) for F baseline JPEGs (capture_stream.py:194/:402), in RGB order (the
     cvtColor(BGR2RGB) of the streams folded in): files u8 [total] device bytes back to back, offsets
     int64 [F+1] device -> out u8 [F,H,W,3] and the int32 status word per file (BF_JPG_* bits).
-    check=True synchronises and raises on any file that did not decode."""
-    _need(files, torch.uint8, "files")
-    _need(offsets, torch.int64, "offsets")
-    F_ = offsets.numel() - 1
-    if F_ < 0:
-        raise HipError("jpeg_decode_rgb: offsets [F+1]")
-    wb = jpeg_workspace_bytes(F_, H, W)
-    if work is None or work.numel() < wb:
-        work = torch.empty(max(wb, 1), dtype=torch.uint8, device=files.device)
-    if out is None:
-        out = torch.empty((F_, H, W, 3), dtype=torch.uint8, device=files.device)
-    _need(out, torch.uint8, "out")
-    if out.numel() != F_ * H * W * 3:
-        raise HipError("jpeg_decode_rgb: out [F,H,W,3]")
-    status = torch.zeros(max(F_, 1), dtype=torch.int32, device=files.device)
-    _check(lib().bf_jpeg_decode_rgb(_ptr(files), _ptr(offsets), c_int(F_), c_int(H), c_int(W), _ptr(out), _ptr(work),
-                                    c_size_t(wb), _ptr(status), _stream()), "bf_jpeg_decode_rgb")
-    if check and F_:
-        st = status[:F_].cpu()
-        bad = torch.nonzero(st).flatten().tolist()
-        if bad:
-            f = bad[0]
-            why = ", ".join(v for k, v in JPEG_STATUS.items() if int(st[f]) & k)
-            raise HipError(f"jpeg_decode_rgb: {len(bad)} of {F_} files did not decode (file {f}: {why})")
-    return out, status[:F_]
+    check=True synchronises and raises on any file that did not decode.  offsets_host: the same
+    offsets on the host, checked against `files` when given (the launch needs no host sizes, so
+    without them nothing is read back and the device offsets are trusted)."""
+    return _decode_batch("jpeg_decode_rgb", lib().bf_jpeg_decode_rgb, jpeg_workspace_bytes, JPEG_STATUS, "file", files,
+                         offsets, H, W, (3,), torch.uint8, out, offsets_host, check, work, sized=False)
 
 
 def jpeg_workspace_bytes(F, H, W):
-    L = lib()
-    L.bf_jpeg_workspace_bytes.restype = c_size_t
-    L.bf_jpeg_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    return int(L.bf_jpeg_workspace_bytes(F, H, W))
+    return int(lib().bf_jpeg_workspace_bytes(F, H, W))
 
 
 def cv2_resize_u8(src, Wd, Hd, out=None):
@@ -1059,6 +1056,17 @@ FP8_MAX = 448.0
 _FP8_OUT = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}
 
 
+def _gemm_fp8_work(a, w, scale, bias=None, act=None, resid=None, out=None, out_dtype=torch.bfloat16,
+                   out_qscale=1.0, plan=None):
+    M, K = a.shape
+    N = w.shape[0]
+    od = out.dtype if out is not None else out_dtype
+    tags = dict(kind="gemm_fp8", act=ACT[act], out=str(od), resid=resid is not None, M=M, N=N, K=K)
+    nbytes = 1.0 * (M * K + N * K) + M * N * od.itemsize + (4.0 * M * N if resid is not None else 0.0)
+    return tags, 2.0 * M * N * K, nbytes
+
+
+@_timed(_gemm_fp8_work)
 def gemm_fp8(a, w, scale, bias=None, act=None, resid=None, out=None, out_dtype=torch.bfloat16,
              out_qscale=1.0, plan=None):
     """out = resid + act(scale * (a @ w.T) + bias); a fp8 e4m3 [M,K], w fp8 [N,K] (per-tensor
@@ -1212,140 +1220,6 @@ def _timer():
         return None
     import threading
     return t if t.thread == threading.get_ident() else None
-
-
-_gemm_untimed = gemm
-_gemm_fp8_untimed = gemm_fp8
-_attention_untimed = attention
-_attention_fp8out_untimed = attention_fp8out
-
-
-def gemm(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype=torch.bfloat16,
-         row_map=None, m=None, plan=None):
-    t = _timer()
-    if t is None:
-        return _gemm_untimed(a, w, bias, act, resid, resid_mod, out, out_dtype, row_map, m, plan)
-    M = a.shape[0] if m is None else m
-    N, K = w.shape
-    ob = (out.dtype if out is not None else out_dtype) == torch.bfloat16
-    tags = dict(kind="gemm", act=ACT[act], out_bf16=ob, resid=resid is not None, M=M, N=N, K=K,
-                large=bool(lib().bf_gemm_large_tiles(c_int(M), c_int(N), c_int(K))))
-    nbytes = 2.0 * (M * K + N * K) + M * N * (2 if ob else 4)
-    if resid is not None:
-        nbytes += 4.0 * (M * N if not resid_mod else resid_mod * N)
-    return t.record(tags, 2.0 * M * N * K, nbytes,
-                    lambda: _gemm_untimed(a, w, bias, act, resid, resid_mod, out, out_dtype, row_map, m, plan))
-
-
-def gemm_fp8(a, w, scale, bias=None, act=None, resid=None, out=None, out_dtype=torch.bfloat16,
-             out_qscale=1.0, plan=None):
-    t = _timer()
-    if t is None:
-        return _gemm_fp8_untimed(a, w, scale, bias, act, resid, out, out_dtype, out_qscale, plan)
-    M, K = a.shape
-    N = w.shape[0]
-    od = out.dtype if out is not None else out_dtype
-    tags = dict(kind="gemm_fp8", act=ACT[act], out=str(od), resid=resid is not None, M=M, N=N, K=K)
-    nbytes = 1.0 * (M * K + N * K) + M * N * od.itemsize + (4.0 * M * N if resid is not None else 0.0)
-    return t.record(tags, 2.0 * M * N * K, nbytes,
-                    lambda: _gemm_fp8_untimed(a, w, scale, bias, act, resid, out, out_dtype, out_qscale, plan))
-
-
-def attention(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs=None, k_bs=None, v_bs=None,
-              o_bs=None, o_map=None, variant=0):
-    t = _timer()
-    if t is None:
-        return _attention_untimed(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs, k_bs, v_bs,
-                                  o_bs, o_map, variant)
-    tags = dict(kind="attn", D=head_dim, sq=sq, sk=sk, batch=batch, heads=heads)
-    bh = float(batch * heads)
-    return t.record(tags, 4.0 * bh * sq * sk * head_dim, 2.0 * bh * head_dim * (2 * sq + 2 * sk),
-                    lambda: _attention_untimed(q, k, v, o, batch, heads, sq, sk, head_dim, scale,
-                                               q_bs, k_bs, v_bs, o_bs, o_map, variant))
-
-
-def attention_fp8out(q, k, v, o, batch, heads, sq, sk, head_dim, scale, out_qscale, q_bs=None,
-                     k_bs=None, v_bs=None, o_bs=None, variant=0):
-    t = _timer()
-    fn = lambda: _attention_fp8out_untimed(q, k, v, o, batch, heads, sq, sk, head_dim, scale, out_qscale,
-                                           q_bs, k_bs, v_bs, o_bs, variant)
-    if t is None:
-        return fn()
-    tags = dict(kind="attn", D=head_dim, sq=sq, sk=sk, batch=batch, heads=heads, fp8out=True)
-    bh = float(batch * heads)
-    return t.record(tags, 4.0 * bh * sq * sk * head_dim, bh * head_dim * (2 * sq + 4 * sk + sq), fn)
-
-
-_depth_preprocess_untimed = depth_preprocess
-_obb_iou_matrix_untimed = obb_iou_matrix
-_nms_scan_untimed = nms_scan
-_fusion_fit_untimed = fusion_fit
-
-
-def obb_iou_matrix(corners):
-    t = _timer()
-    if t is None:
-        return _obb_iou_matrix_untimed(corners)
-    n = int(corners.shape[0])
-    # work = box pairs (i < j) of the IoU matrix (gate + 25^3 grid count launches)
-    return t.record(dict(kind="obb_iou", n=n), n * (n - 1) / 2.0, 96.0 * n + 8.0 * n * n,
-                    lambda: _obb_iou_matrix_untimed(corners))
-
-
-def nms_scan(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_num, cfg, out=None):
-    t = _timer()
-    fn = lambda: _nms_scan_untimed(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_num,
-                                   cfg, out)
-    if t is None:
-        return fn()
-    n = int(scores.shape[0])
-    return t.record(dict(kind="nms_scan", n=n), float(n), 8.0 * n * n, fn)
-
-
-def fusion_fit(view_off, n_views, view_box, view_R, view_score, view_pose, view_tc, pst, cfg,
-               trace=False, max_views=None, packed_out=False, packed=None):
-    t = _timer()
-    fn = lambda: _fusion_fit_untimed(view_off, n_views, view_box, view_R, view_score, view_pose, view_tc,
-                                     pst, cfg, trace, max_views, packed_out, packed)
-    if t is None:
-        return fn()
-    res = []
-    nj = int(view_off.shape[0])
-    P = int(cfg.pst_size)
-    # work = particle-view fitness evaluations: sum over jobs of views * particles * iterations
-    # (the iteration counts are read when the summary is taken)
-    work = lambda: float((res[0][1][nj:2 * nj].long() * n_views.long()).sum().item() * P if packed_out
-                         else (res[0][2].long() * n_views.long()).sum().item() * P)
-    t.record(dict(kind="fusion_fit", jobs=nj), work, 0.0, lambda: res.append(fn()))
-    return res[0]
-
-
-def depth_preprocess(depth, K=None, RT=None, max_depth=10.0, out=None, params=None, xyz=None, valid=None,
-                     ws=None):
-    t = _timer()
-    if t is None:
-        return _depth_preprocess_untimed(depth, K, RT, max_depth, out, params, xyz, valid, ws)
-    b, h, w = depth.shape
-    # outputs and workspace allocated before the start event: the events bracket the launches only
-    out = torch.empty_like(depth) if out is None else out
-    params = torch.empty((b, 2), dtype=torch.float32, device=depth.device) if params is None else params
-    if K is not None:
-        xyz = torch.empty((b, h, w, 3), dtype=torch.float32, device=depth.device) if xyz is None else xyz
-        valid = torch.empty((b, h, w), dtype=torch.uint8, device=depth.device) if valid is None else valid
-    if ws is None and not torch.cuda.is_current_stream_capturing():
-        ws = depth_workspace(b, h, w, depth.device)
-    fn = lambda: _depth_preprocess_untimed(depth, K, RT, max_depth, out, params, xyz, valid, ws)
-    n = float(b * h * w)
-    # algorithmic bytes: read the depth once, write the standardised map (+ xyz and
-    # the valid mask when back-projecting)
-    nbytes = 8.0 * n + (13.0 * n if K is not None else 0.0)
-    tags = dict(kind="depth", backproject=K is not None, b=b, h=h, w=w)
-    return t.record(tags, 0.0, nbytes, fn)
-
-
-def depth_standardize(depth, out=None, params=None, ws=None):
-    """depth f32[b,h,w] -> (standardised f32[b,h,w], params f32[b,2])"""
-    return depth_preprocess(depth, out=out, params=params, ws=ws)
 
 
 def new_depth_workspace(b, h, w, device):

@@ -146,8 +146,8 @@ def decode_color_jpegs(blobs, H, W, device="cuda"):
     baseline JPEG files (their bytes), decoded on the GPU (bf_jpeg_decode_rgb) -> u8 [F, H, W, 3]
     RGB on device; raises if any file does not decode"""
     from boxfusion_amd import _lib
-    files, offs, _ = upload_files(blobs, device)
-    out, _ = _lib.jpeg_decode_rgb(files, offs, H, W)
+    files, offs, offs_h = upload_files(blobs, device)
+    out, _ = _lib.jpeg_decode_rgb(files, offs, H, W, offsets_host=offs_h)
     return out
 
 
