@@ -1051,6 +1051,201 @@ def cv2_resize_u8(src, Wd, Hd, out=None):
         return out[0, :, :, 0]
     return out[0] if src.dim() == 3 else out
 
+
+# ------------------------------------------------------------------------------------------
+# coloured scene point cloud (bf_cloud.hip)
+# ------------------------------------------------------------------------------------------
+def _pil_bicubic(x):
+    # Pillow's bicubic_filter (a = -0.5), the same f64 expressions
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+@functools.lru_cache(maxsize=64)
+def pil_bicubic_coeffs(n_in, n_out):
+    """Pillow's 8-bit resample tables of one axis for Image.resize's default BICUBIC, n_in -> n_out
+    pixels (precompute_coeffs + normalize_coeffs_8bpc, all in f64 on the host): (bounds int32
+    [n_out,2] = first source pixel and tap count, coeffs int32 [n_out,ksize] = the normalised weights
+    as int(w * 2^22 -+ 0.5), zero past the tap count).  The arrays are cached: do not write to them."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise HipError("pil_bicubic_coeffs: sizes must be positive")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    bounds = np.zeros((n_out, 2), np.int32)
+    coeffs = np.zeros((n_out, ksize), np.int32)
+    ss = 1.0 / fs
+    for i in range(n_out):
+        c = (i + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        xmax = min(int(c + support + 0.5), n_in) - xmin
+        w = [_pil_bicubic((x + xmin - c + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[i] = (xmin, xmax)
+        coeffs[i, :xmax] = [int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22)) for v in w]
+    bounds.setflags(write=False)
+    coeffs.setflags(write=False)
+    return bounds, coeffs
+
+
+_BICUBIC_DEV = {}
+
+
+def _bicubic_tables(n_in, n_out, device):
+    """pil_bicubic_coeffs on the device, uploaded once per (in, out, device)"""
+    key = (int(n_in), int(n_out), torch.device(device).index)
+    t = _BICUBIC_DEV.get(key)
+    if t is None:
+        b, k = pil_bicubic_coeffs(n_in, n_out)
+        t = _BICUBIC_DEV[key] = (h2d(b.copy(), device), h2d(k.copy(), device))
+    return t
+
+
+def _resize_bicubic_work(src, Hd, Wd, out=None):
+    n_in, n_out = float(src.numel()), float(src.numel() // (src.shape[-3] * src.shape[-2]) * Hd * Wd)
+    return dict(kind="resize_bicubic", Hd=Hd, Wd=Wd), 0.0, n_in + n_out
+
+
+@_timed(_resize_bicubic_work)
+def resize_bicubic_u8(src, Hd, Wd, out=None):
+    """Image.fromarray(img).resize((Wd, Hd)) (Pillow's default BICUBIC, 8-bit path, bit-exact) of RGB
+    images u8 [H,W,3] or [F,H,W,3] on the device (bf_resize_bicubic_u8)"""
+    _need(src, torch.uint8, "src")
+    x = src[None] if src.dim() == 3 else src
+    if x.dim() != 4 or x.shape[-1] != 3:
+        raise HipError("resize_bicubic_u8: RGB images [F,H,W,3]")
+    x = x.contiguous()
+    F_, Hs, Ws, _ = x.shape
+    Hd, Wd = int(Hd), int(Wd)
+    if out is None:
+        out = torch.empty((F_, Hd, Wd, 3), dtype=torch.uint8, device=x.device)
+    _need(out, torch.uint8, "out")
+    if out.numel() != F_ * Hd * Wd * 3:
+        raise HipError("resize_bicubic_u8: out [F,Hd,Wd,3]")
+    bx, kx = _bicubic_tables(Ws, Wd, x.device) if Ws != Wd else (None, None)
+    by, ky = _bicubic_tables(Hs, Hd, x.device) if Hs != Hd else (None, None)
+    tmp = (torch.empty((F_, Hs, Wd, 3), dtype=torch.uint8, device=x.device)
+           if Ws != Wd and Hs != Hd else None)
+    _check(lib().bf_resize_bicubic_u8(_ptr(x), c_int(F_), c_int(Hs), c_int(Ws), c_int(Hd), c_int(Wd), _ptr(kx),
+                                      _ptr(bx), c_int(kx.shape[1] if kx is not None else 0), _ptr(ky), _ptr(by),
+                                      c_int(ky.shape[1] if ky is not None else 0), _ptr(tmp), _ptr(out),
+                                      _stream()), "bf_resize_bicubic_u8")
+    return out[0] if src.dim() == 3 else out
+
+
+def _cloud_blocks(items, groups):
+    L = lib()
+    L.bf_cloud_blocks.restype, L.bf_cloud_blocks.argtypes = c_size_t, [ctypes.c_longlong, c_int]
+    return max(int(L.bf_cloud_blocks(int(items), int(groups))), 1)
+
+
+def _cloud_inputs(name, xyz, valid, rgb):
+    """(xyz f32 [B,H,W,3], valid u8 [B,H,W], rgb u8 [B,H,W,3]) contiguous, shapes checked"""
+    xyz = _need(xyz, torch.float32, f"{name}: xyz").contiguous()
+    if valid.dtype == torch.bool:
+        valid = valid.contiguous().view(torch.uint8)
+    valid = _need(valid, torch.uint8, f"{name}: valid").contiguous()
+    rgb = _need(rgb, torch.uint8, f"{name}: rgb").contiguous()
+    if xyz.dim() != 4 or xyz.shape[-1] != 3 or tuple(valid.shape) != tuple(xyz.shape[:3]) or rgb.shape != xyz.shape:
+        raise HipError(f"{name}: xyz [B,H,W,3], valid [B,H,W], rgb [B,H,W,3]; got {tuple(xyz.shape)}, "
+                       f"{tuple(valid.shape)}, {tuple(rgb.shape)}")
+    return xyz, valid, rgb
+
+
+def _cloud_pack_work(xyz, valid, rgb):
+    n = float(valid.numel())
+    # algorithmic bytes: the mask twice, xyz + rgb read and six floats written per pixel at most
+    return dict(kind="cloud_pack", n=int(n)), 0.0, n * (2 + 12 + 3 + 24)
+
+
+@_timed(_cloud_pack_work)
+def cloud_pack(xyz, valid, rgb):
+    """torch.cat((xyz, rgb / 255.0), -1)[valid] (demo.py:127) for a batch (bf_cloud_pack): xyz f32
+    [B,H,W,3], valid bool / u8 [B,H,W], rgb u8 [B,H,W,3] -> (xyzrgb f32 [B*H*W,6], offsets int32
+    [B+1]); frame b's rows are offsets[b]..offsets[b+1], rows past offsets[B] are not written"""
+    xyz, valid, rgb = _cloud_inputs("cloud_pack", xyz, valid, rgb)
+    B, H, W = valid.shape
+    out = torch.empty((B * H * W, 6), dtype=torch.float32, device=xyz.device)
+    offsets = torch.empty(B + 1, dtype=torch.int32, device=xyz.device)
+    work = torch.empty(_cloud_blocks(H * W, B), dtype=torch.int32, device=xyz.device)
+    _check(lib().bf_cloud_pack(_ptr(xyz), _ptr(valid), _ptr(rgb), c_int(B), c_int(H), c_int(W), _ptr(out),
+                               _ptr(offsets), _ptr(work), _stream()), "bf_cloud_pack")
+    return out, offsets
+
+
+CLOUD_SLOT_WORDS = 5            # int64 words of a voxel slot: key, then eight uint32 (bf_cloud_integrate)
+CLOUD_STATS = ("stored", "nonfinite", "out_of_range", "dropped_full", "saturated", "runs")
+
+
+def cloud_table(capacity, device):
+    """(table int64 [capacity,5] with every key empty, stats int64 [8] zeroed) for cloud_integrate"""
+    capacity = int(capacity)
+    if capacity <= 0 or capacity & (capacity - 1) or capacity >= 1 << 31:
+        raise HipError("cloud_table: capacity must be a power of two below 2^31")
+    table = torch.zeros((capacity, CLOUD_SLOT_WORDS), dtype=torch.int64, device=device)
+    table[:, 0] = -1
+    return table, torch.zeros(8, dtype=torch.int64, device=device)
+
+
+def _cloud_integrate_work(xyz, valid, rgb, fine_step, table, stats, merge=True):
+    n = float(valid.numel())
+    return dict(kind="cloud_integrate", n=int(n), merge=bool(merge)), 0.0, n * (1 + 12 + 3)
+
+
+@_timed(_cloud_integrate_work)
+def cloud_integrate(xyz, valid, rgb, fine_step, table, stats, merge=True):
+    """the valid points of xyz f32 [...,3] / valid bool or u8 [...] / rgb u8 [...,3] into the voxel
+    map `table` (cloud_table; bf_cloud_integrate); fine_step = voxel / 256 as an f32"""
+    xyz = _need(xyz, torch.float32, "cloud_integrate: xyz").contiguous()
+    if valid.dtype == torch.bool:
+        valid = valid.contiguous().view(torch.uint8)
+    valid = _need(valid, torch.uint8, "cloud_integrate: valid").contiguous()
+    rgb = _need(rgb, torch.uint8, "cloud_integrate: rgb").contiguous()
+    n = valid.numel()
+    if xyz.numel() != 3 * n or rgb.numel() != 3 * n:
+        raise HipError("cloud_integrate: xyz [...,3], valid [...], rgb [...,3] of the same points")
+    _need(table, torch.int64, "cloud_integrate: table")
+    _need(stats, torch.int64, "cloud_integrate: stats")
+    if table.dim() != 2 or table.shape[1] != CLOUD_SLOT_WORDS or stats.numel() < 8:
+        raise HipError("cloud_integrate: table [capacity,5] / stats [8] of cloud_table")
+    _check(lib().bf_cloud_integrate(_ptr(xyz), _ptr(valid), _ptr(rgb), ctypes.c_longlong(n), c_float(float(fine_step)),
+                                    _ptr(table), ctypes.c_longlong(table.shape[0]), _ptr(stats),
+                                    c_int(int(bool(merge))), _stream()), "bf_cloud_integrate")
+
+
+def _cloud_extract_work(table):
+    return dict(kind="cloud_extract", capacity=int(table.shape[0])), 0.0, 48.0 * table.shape[0]
+
+
+@_timed(_cloud_extract_work)
+def cloud_extract(table):
+    """the occupied slots of a voxel map in slot order (bf_cloud_extract): (key int64 [cap], count
+    int32 [cap] holding the uint32 counts, sums int32 [cap,6] holding the uint32 sums, n int32 [1] on
+    the device); rows past n are not written"""
+    _need(table, torch.int64, "cloud_extract: table")
+    cap, dev = table.shape[0], table.device
+    key = torch.empty(cap, dtype=torch.int64, device=dev)
+    count = torch.empty(cap, dtype=torch.int32, device=dev)
+    sums = torch.empty((cap, 6), dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
+    _check(lib().bf_cloud_extract(_ptr(table), ctypes.c_longlong(cap), _ptr(key), _ptr(count), _ptr(sums), _ptr(n),
+                                  _ptr(work), _stream()), "bf_cloud_extract")
+    return key, count, sums, n
+
+
 FP8 = torch.float8_e4m3fn      # OCP e4m3 (gfx950's fp8; not the MI300 fnuz variant)
 FP8_MAX = 448.0
 _FP8_OUT = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}

@@ -146,6 +146,7 @@ class DetectStage:
             dstd, params, xyz, valid = _lib.depth_preprocess(self.in_depth, self.Kd_dev, self.in_pose, 10.0,
                                                              ws=self.ds_ws)
             self.out["xyz"] = [(xyz[b], valid[b]) for b in range(B)]
+            self.out["xyz_batch"] = (xyz, valid)
         else:
             dstd, params = _lib.depth_standardize(self.in_depth, ws=self.ds_ws)
         res = self.cutr(self.in_rgb, dstd, params, self.K_dev, self.in_Tg, [(H, W)] * B,
@@ -184,8 +185,8 @@ class DetectStage:
     def preprocess_frames(self, depth, poses):
         """demo.py:121-131 on frames that are not keyframes: depth standardisation (Preprocessor)
         and, with backproject, the unproject of the same depth (viz_on_gt_points, on by default)
-        -- one bf_depth_preprocess pass over any number of frames.  Nothing reads the results
-        back (in the reference they feed rerun only); they stay in self.last_frames."""
+        -- one bf_depth_preprocess pass over any number of frames.  The results stay in
+        self.last_frames; Pipeline.run's scene cloud and /world/xyz options read the points."""
         n = depth.shape[0]
         self.last_frames = None          # release the previous call's outputs before allocating
         if self.backproject:
@@ -215,7 +216,7 @@ class DetectStage:
         self.in_pose.copy_(torch.from_numpy(poses))
         self._run_device()
         o = self.out
-        self.last = dict(xyz=o.get("xyz"), keep=o["keep"], res=o["res"])
+        self.last = dict(xyz=o.get("xyz"), xyz_batch=o.get("xyz_batch"), keep=o["keep"], res=o["res"])
         if "clip" in o:
             self.last["clip"] = o["clip"]
         if not return_instances:
@@ -261,6 +262,16 @@ def scene_instances(det, device, H=480, W=640):
     return p
 
 
+def _frame_points(stage, what):
+    """(xyz [b,h,w,3], valid [b,h,w]) of the frames a detect stage just worked on: `what` is its
+    .last dict (a keyframe batch) or preprocess_frames' return value (non-keyframes)"""
+    got = what.get("xyz_batch") if isinstance(what, dict) else (what[2:4] if what is not None and len(what) == 4 else None)
+    if got is None:
+        raise ValueError(f"{type(stage).__name__} keeps no back-projected points (backproject=True is needed "
+                         "for cloud= / viz_points=)")
+    return got
+
+
 def _viz_images(viz, rgb, depth, j):
     """(image, depth) of frame j on the host for a FrameLogger that logs images (demo.py:180-190
     logs the RGB frame and the raw depth of every frame); (None, None) otherwise"""
@@ -277,7 +288,8 @@ class Pipeline:
     def __init__(self, detect: DetectStage, fusion: FusionStage, gap):
         self.detect, self.fusion, self.gap = detect, fusion, gap
 
-    def run(self, frames, n_frames, per_frame=True, frames_per_call=64, viz=None):
+    def run(self, frames, n_frames, per_frame=True, frames_per_call=64, viz=None, cloud=None,
+            cloud_frames="keyframes", viz_points=False):
         """frames(ids) -> (rgb [b,H,W,3] u8 dev, depth [b,H,W] f32 dev, poses [b,4,4] host).
         A frames callable that takes a `need_rgb` keyword is called with need_rgb=False for the
         non-keyframes whose RGB nothing reads (their per-frame work uses depth and pose only) and
@@ -286,14 +298,38 @@ class Pipeline:
         (DetectStage.preprocess_frames, up to `frames_per_call` frames per call).
         viz: a visualize.FrameLogger -- demo.py's per-frame rerun calls (pose, pinhole, image,
         depth, trajectory) for every frame in frame order and the global boxes after each
-        keyframe's fusion (host side, after the frame's GPU work; not used by the bench)."""
+        keyframe's fusion (host side, after the frame's GPU work; not used by the bench).
+        cloud: a scene_cloud.SceneCloud that takes the back-projected, coloured points of every
+        keyframe batch (cloud_frames="keyframes") or of every frame (cloud_frames="all", which needs
+        per_frame and asks the frame source for the non-keyframes' RGB), enqueued on the current
+        stream right after the work that produced them and before the input buffers are reused.
+        viz_points: hand viz.frame the frame's xyzrgb (demo.py:193's /world/xyz; read back per
+        batch).  All three are off by default."""
+        if cloud_frames not in ("keyframes", "all"):
+            raise ValueError("cloud_frames: 'keyframes' or 'all'")
+        if cloud is not None and cloud_frames == "all" and not per_frame:
+            raise ValueError("cloud_frames='all' needs per_frame=True (the non-keyframes' depth work)")
+        viz_points = bool(viz_points) and viz is not None
+        cloud_all = cloud is not None and cloud_frames == "all"
         B = self.detect.B
         kf = [i for i in range(n_frames) if i % self.gap == 0]
         try:
             lazy_rgb = "need_rgb" in inspect.signature(frames).parameters
         except (TypeError, ValueError):
             lazy_rgb = False
-        nk_rgb = viz is not None and getattr(viz, "log_images", False)
+        nk_rgb = (viz is not None and getattr(viz, "log_images", False)) or cloud_all or viz_points
+
+        def points(xyz, valid, rgb, n, integrate):
+            # the first n frames' points: into the map, and / or as per-frame host rows for the viewer
+            from boxfusion_amd.scene_cloud import frame_cloud
+            xyz, valid, rgb = xyz[:n], valid[:n], rgb[:n]
+            if integrate:
+                cloud.integrate(xyz, valid, rgb)
+            if not viz_points:
+                return [None] * n
+            rows, off = frame_cloud(xyz, valid, rgb)
+            rows, off = rows.cpu().numpy(), off.cpu().tolist()
+            return [rows[off[j]:off[j + 1]] for j in range(n)]
 
         def nk_frames(ids_):
             return frames(ids_, need_rgb=nk_rgb) if lazy_rgb else frames(ids_)
@@ -305,11 +341,16 @@ class Pipeline:
                 nk = [i for i in range(ids[0], min(ids[-1] + self.gap, n_frames)) if i % self.gap != 0]
                 for c in range(0, len(nk), frames_per_call):
                     _rgb, depth, poses = nk_frames(nk[c:c + frames_per_call])
-                    self.detect.preprocess_frames(depth.contiguous(), poses)
+                    done = self.detect.preprocess_frames(depth.contiguous(), poses)
                     self.frames_preprocessed += len(nk[c:c + frames_per_call])
+                    pts = None
+                    if cloud_all or viz_points:
+                        pts = points(*_frame_points(self.detect, done), _rgb, len(poses), cloud_all)
                     if viz is not None:
                         for j, i in enumerate(nk[c:c + frames_per_call]):
                             nk_pose[i] = (np.asarray(poses[j]),) + _viz_images(viz, _rgb, depth, j)
+                            if viz_points:
+                                nk_pose[i] += (pts[j],)
             rgb, depth, poses = frames(ids)
             if len(ids) < B:   # ragged tail: pad the batch with the last frame, drop its results
                 pad = B - len(ids)
@@ -317,12 +358,17 @@ class Pipeline:
                 depth = torch.cat([depth, depth[-1:].expand(pad, -1, -1)])
                 poses = np.concatenate([poses, np.repeat(poses[-1:], pad, 0)])
             preds = self.detect(rgb.contiguous(), depth.contiguous(), poses)
+            pts = None
+            if cloud is not None or viz_points:
+                # the stage's own input copy of the frames when it has one (what its kernels read)
+                pts = points(*_frame_points(self.detect, getattr(self.detect, "last", None) or {}),
+                             getattr(self.detect, "in_rgb", rgb), len(ids), cloud is not None)
             for j, i in enumerate(ids):
                 self.fusion.keyframe(i, poses[j], preds[j])
                 if viz is not None:
                     # demo.py order: keyframe i's frame logs, its boxes after the fusion step, then
                     # the frames up to the next keyframe (the trajectory grows frame by frame)
-                    viz.frame(i, poses[j], *_viz_images(viz, rgb, depth, j))
+                    viz.frame(i, poses[j], *_viz_images(viz, rgb, depth, j), *([pts[j]] if viz_points else []))
                     viz.boxes(self.fusion.all_pred_box, i)
                     for f in range(i + 1, min(i + self.gap, n_frames)):
                         if f in nk_pose:

@@ -7,7 +7,7 @@ color/*.jpg, depth/*.png, pose/*.txt tree.
 of `DecodedFrameStream` for the exported tree of the same scene, the colour frames through
 bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zlib on the host);
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
-the header.
+the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud (no model needed).
 
 Layout (little-endian, packed): uint32 version (4), uint64 n + n bytes sensor name, four row-major
 4x4 float32 matrices (colour intrinsics / extrinsics, depth intrinsics / extrinsics), int32 colour
@@ -279,6 +279,20 @@ def info(sens, out=None):
               file=out)
 
 
+def cloud(sens, voxel=0.02, start=0, stop=None, step=1, max_depth=10.0, capacity=1 << 22, device="cuda", batch=16):
+    """the scene as a voxel map: every selected frame through SensFrameStream, demo.py:123-126's
+    unproject of its depth with gt.depth.K and gt.RT, coloured by its image, into a SceneCloud
+    (returned)"""
+    from boxfusion_amd.scene_cloud import SceneCloud
+    from boxfusion_amd.tools_utils import unproject
+    sc = SceneCloud(voxel=voxel, capacity=capacity, device=device)
+    for sample in SensFrameStream(sens, device=device, batch=batch, start=start, stop=stop, step=step):
+        gt = sample["sensor_info"].gt
+        xyz, valid = unproject(sample["wide"]["depth"][-1], gt.depth.K[-1], gt.RT[-1], max_depth=max_depth)
+        sc.integrate(xyz, valid, sample["wide"]["image"][-1].permute(1, 2, 0).contiguous())
+    return sc
+
+
 def main(argv=None):
     import argparse
     p = argparse.ArgumentParser(prog="python -m boxfusion_amd.sens", description="ScanNet .sens containers")
@@ -291,10 +305,30 @@ def main(argv=None):
     pe.add_argument("--start", type=int, default=0)
     pe.add_argument("--stop", type=int, default=None)
     pe.add_argument("--step", type=int, default=1)
+    pc = sub.add_parser("cloud", help="write the scene's coloured point cloud (a voxel map) as a PLY")
+    pc.add_argument("sens")
+    pc.add_argument("out")
+    pc.add_argument("--voxel", type=float, default=0.02, help="voxel edge in metres")
+    pc.add_argument("--start", type=int, default=0)
+    pc.add_argument("--stop", type=int, default=None)
+    pc.add_argument("--step", type=int, default=1)
+    pc.add_argument("--max-depth", type=float, default=10.0)
     a = p.parse_args(argv)
+    if a.cmd == "cloud":
+        if not a.voxel > 0:
+            p.error("--voxel must be positive")
+        if a.step < 1:
+            p.error("--step must be at least 1")
+        if not a.max_depth > 0:
+            p.error("--max-depth must be positive")
     with SensFile(a.sens) as s:
         if a.cmd == "info":
             info(s)
+        elif a.cmd == "cloud":
+            sc = cloud(s, a.voxel, a.start, a.stop, a.step, a.max_depth)
+            n = sc.save_ply(a.out)
+            print(f"{n} points -> {a.out}")
+            print(" ".join(f"{k}={v}" for k, v in sc.stats().items()))
         else:
             frames = export(s, a.out, a.start, a.stop, a.step)
             print(f"{len(frames)} frames -> {a.out}")

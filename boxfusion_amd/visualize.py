@@ -225,6 +225,40 @@ def read_ply_mesh(path):
             f["i"].copy())
 
 
+_POINT_DT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def points_to_ply(xyz, rgb, path):
+    """a coloured point cloud (xyz [n,3] float, rgb [n,3] u8) as a binary little-endian PLY: float
+    x y z and uchar red green blue per vertex, no faces"""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    if len(xyz) != len(rgb):
+        raise ValueError(f"points_to_ply: {len(xyz)} positions, {len(rgb)} colours")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    v = np.empty(len(xyz), _POINT_DT)
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+
+
+def read_ply_points(path):
+    """the positions f32 [n,3] and colours u8 [n,3] of a PLY written by points_to_ply"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    nv = int([h for h in head if h.startswith("element vertex")][0].split()[-1])
+    v = np.frombuffer(data, _POINT_DT, nv, end)
+    return (np.stack([v["x"], v["y"], v["z"]], 1).reshape(-1, 3),
+            np.stack([v["red"], v["green"], v["blue"]], 1).reshape(-1, 3))
+
+
 class FrameLogger:
     """demo.py:93-197's per-frame log calls in the reference's order: set_time, camera pose +
     pinhole on /world/image and /device/wide/image, the RGB image, the depth image and its

@@ -633,6 +633,51 @@ int bf_ingest_rgbd(const uint8_t* bgr, int Hc, int Wc, const uint16_t* depth, in
 int bf_cv2_resize_u8(const uint8_t* src, int Hs, int Ws, int cn, int Hd, int Wd, int F, uint8_t* dst,
                      void* stream);
 
+/* ---- coloured scene point cloud (reference: demo.py:121-127 builds xyzrgb per frame, :193 logs it
+ * as /world/xyz and rerun accumulates it; here the accumulation is a voxel map on the device) ----
+ *
+ * Image.fromarray(image).resize((Wd, Hd)) (demo.py:124): Pillow's default BICUBIC on 8-bit RGB,
+ * src u8 [F,Hs,Ws,3] -> dst u8 [F,Hd,Wd,3], bit-exact to Pillow's 8-bit path: the horizontal pass
+ * into tmp u8 [F,Hs,Wd,3] (needed only when both sizes change), then the vertical pass; a pass whose
+ * size does not change is skipped.  kx int32 [Wd,ksx] / bx int32 [Wd,2] (first tap, tap count) and
+ * ky [Hd,ksy] / by [Hd,2] are Pillow's 22-bit integer coefficient and bounds tables, computed on the
+ * host and uploaded by the caller (device pointers; those of a skipped pass may be NULL). */
+int bf_resize_bicubic_u8(const uint8_t* src, int F, int Hs, int Ws, int Hd, int Wd, const int* kx,
+                         const int* bx, int ksx, const int* ky, const int* by, int ksy, uint8_t* tmp,
+                         uint8_t* dst, void* stream);
+
+/* entries of the block_counts workspace of bf_cloud_pack (items_per_group = H*W, groups = B) and of
+ * bf_cloud_extract (items_per_group = capacity, groups = 1) */
+size_t bf_cloud_blocks(long long items_per_group, int groups);
+
+/* torch.cat((xyz, matched_image / 255.0), dim=-1)[valid] (demo.py:127) for B frames: xyz f32
+ * [B,H,W,3], valid u8 [B,H,W], rgb u8 [B,H,W,3] (at the depth size) -> xyzrgb f32 [B*H*W,6], of
+ * which rows offsets[b] .. offsets[b+1] are frame b's valid pixels in row-major order (offsets
+ * int32 [B+1], device); colours are (float)v / 255.0f.  block_counts: int32
+ * [bf_cloud_blocks(H*W, B)] scratch. */
+int bf_cloud_pack(const float* xyz, const uint8_t* valid, const uint8_t* rgb, int B, int H, int W,
+                  float* xyzrgb, int* offsets, int* block_counts, void* stream);
+
+/* The valid points of n pixels (xyz f32 [n,3], valid u8 [n], rgb u8 [n,3]) into a voxel hash map.
+ * Per axis f = floorf(x / fine_step) with fine_step = voxel / 256 (f32), voxel index f >> 8,
+ * in-voxel offset f & 255.  table: uint64 [capacity,5], capacity a power of two; a slot is the key
+ * (three 21-bit indices biased by 2^20, x << 42 | y << 21 | z; all ones = empty) and eight uint32:
+ * count, the three offset sums, the three colour sums, 0.  A new table has every key all ones and
+ * everything else zero.  Integer adds only, so the contents do not depend on the order of arrival;
+ * merge != 0 sums runs of equal keys over adjacent lanes first (same contents, fewer atomics).
+ * stats: uint64 [8], added to: points stored, non-finite (skipped), index outside +-2^20 (skipped),
+ * dropped because neither the key nor an empty slot was found in capacity probes, refused by a voxel
+ * that holds 2^24 points, runs (sets of atomic adds issued), 0, 0. */
+int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint8_t* rgb, long long n,
+                       float fine_step, void* table, long long capacity, void* stats, int merge,
+                       void* stream);
+
+/* the occupied slots of a bf_cloud_integrate table in slot order: key int64 [capacity], count uint32
+ * [capacity], sums uint32 [capacity,6] (offset x y z, colour r g b), of which the first *n_out
+ * (int32, device) rows are written.  block_counts: int32 [bf_cloud_blocks(capacity, 1)] scratch. */
+int bf_cloud_extract(const void* table, long long capacity, int64_t* key, uint32_t* count,
+                     uint32_t* sums, int* n_out, int* block_counts, void* stream);
+
 /* ---- depth PNG decode (reference: cv2.imread(depth_path, cv2.IMREAD_UNCHANGED),
  * capture_stream.py:197 ScanNet / :405 CA-1M) ----
  * F PNG files, back to back in device memory: file f = files[offsets[f] .. offsets[f+1]) (offsets
