@@ -280,9 +280,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(
 // (record() only counts them: order-free).  The list / keep edits stay on lane 0 in the
 // reference's order, so the results are those of k_nms_scan.
 // ------------------------------------------------------------------------------------------
-#ifndef NMS_FAST_N
-#define NMS_FAST_N 96       // (a diagnostic build sets 0 to run k_nms_scan everywhere)
-#endif
+#define NMS_FAST_N 96
 #define NMS_FAST_LDS_MAX (150 * 1024)
 
 __device__ __forceinline__ unsigned long long lanes_lt_mask() {
@@ -295,9 +293,6 @@ __device__ __forceinline__ unsigned long long lanes_lt_mask() {
 // boxes' init ids and their fusion-list entries); a lookup whose slot holds another frame reads
 // the pose from global memory instead, so every pose value is the same either way.
 #define NMS_PC 256
-#ifndef NMS_DIAG_NORECORD
-#define NMS_DIAG_NORECORD 0     // timing diagnostic only (wrong results): the scan without record()
-#endif
 __device__ __forceinline__ const float* nms_pose(const float* poses, const int* ptag, const float* pcache,
                                                  int f) {
     const int slot = f & (NMS_PC - 1);
@@ -491,7 +486,7 @@ __global__ void __launch_bounds__(64) k_nms_scan_w(
             // BoxManager.record(cur=i, fusion_inds=supp)
             const int cur = i;
             const float* ccur = cen + 3 * cur;
-            for (int s = 0; s < (NMS_DIAG_NORECORD ? 0 : nsupp); ++s) {
+            for (int s = 0; s < nsupp; ++s) {
                 const int idx = supp[s];
                 const float* cidx = cen + 3 * idx;
                 float dx = ccur[0] - cidx[0], dy = ccur[1] - cidx[1], dz = ccur[2] - cidx[2];
@@ -601,7 +596,7 @@ BF_API int bf_nms_scan_ws(const double* iou, const float* corners, const float* 
                            keep, n_keep, success, n_success, events, n_events, status, *cfg, nullptr);
         return bf_check_launch();
     }
-    if (workspace && NMS_FAST_N > 0 && nms_fast_lds(n, cfg->list_capacity, true) <= NMS_FAST_LDS_MAX) {
+    if (workspace && nms_fast_lds(n, cfg->list_capacity, true) <= NMS_FAST_LDS_MAX) {
         const int words = nms_words(n);
         auto* bits = static_cast<unsigned long long*>(workspace);
         hipLaunchKernelGGL(k_nms_bits, dim3(bf_cdiv(n * words, 4)), dim3(256), 0, st, iou, n, words,

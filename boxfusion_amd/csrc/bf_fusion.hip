@@ -24,12 +24,6 @@
 #include "bf_common.h"
 
 #define FUSE_MAX_VIEWS 32
-#ifndef FUSE_SPLIT_ITER
-// 1: terms and step as two launches per iteration (default: measured faster under the detect
-// load — the one-launch form's device-scope fences write back L2 in every workgroup);
-// 0 (diagnostic build): k_fuse_iter, one launch per iteration
-#define FUSE_SPLIT_ITER 1
-#endif
 #define FUSE_MAX_PST 1024
 #define CAND_CAP 64
 
@@ -156,25 +150,6 @@ __device__ float iou_hulls(P2* c0, P2* ct, int* flags) {
     return iou_hull_pre(c0, ht, nt, polygon_area(ht, nt), flags);
 }
 
-// ------------------------------------------------------------------------------------------
-// LDS form of iou_hull_pre for the refinement loop (same arithmetic, same results).
-// The scratch form keeps ~2 KB of per-thread arrays (hull stacks, 64 candidates) that spill
-// to L2 at this kernel's occupancy; here one wave's stacks live in LDS, element e of lane l
-// at [e * 64 + l], and the 8 projected corners are sorted in registers by a 19-comparator
-// network (any correct sort gives the exchange sort's order: equal keys are equal points).
-// Lanes with more than FAST_CAND candidates (never seen on real boxes: two convex 8-gons give
-// at most 16 vertices + 16 crossings in general position) take the scratch path.
-// ------------------------------------------------------------------------------------------
-#ifndef FAST_CAND
-#define FAST_CAND 32   // (a diagnostic build lowers it to exercise the scratch path)
-#endif
-struct HullLds {
-    P2 cand[FAST_CAND * 64];   // candidates, sorted; then the lower chain in place
-    P2 up[FAST_CAND * 64];     // upper chain of the candidate hull
-    P2 lo0[8 * 64];            // lower chain of hull(c0)
-    P2 up0[8 * 64];            // upper chain of hull(c0)
-};
-
 __device__ __forceinline__ bool p2_greater(P2 a, P2 b) {
     return a.x > b.x || (a.x == b.x && a.y > b.y);
 }
@@ -186,139 +161,30 @@ __device__ __forceinline__ void p2_cswap(P2& a, P2& b) {
     b = hi;
 }
 
-// hull vertex i of a monotone-chain hull stored as lower[0..nl-1) ++ upper[0..nu-1)
-#define HULL_AT(lo, up, nl1, i) ((i) < (nl1) ? (lo)[(i) * 64] : (up)[((i) - (nl1)) * 64])
-
-__device__ float iou_hull_lds(const P2* c0in, const P2* ht, int nt, float at, HullLds& L,
-                              int lane, int* flags) {
-    P2 c[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c[j] = c0in[j];
-    p2_cswap(c[0], c[2]); p2_cswap(c[1], c[3]); p2_cswap(c[4], c[6]); p2_cswap(c[5], c[7]);
-    p2_cswap(c[0], c[4]); p2_cswap(c[1], c[5]); p2_cswap(c[2], c[6]); p2_cswap(c[3], c[7]);
-    p2_cswap(c[0], c[1]); p2_cswap(c[2], c[3]); p2_cswap(c[4], c[5]); p2_cswap(c[6], c[7]);
-    p2_cswap(c[2], c[4]); p2_cswap(c[3], c[5]);
-    p2_cswap(c[1], c[4]); p2_cswap(c[3], c[6]);
-    p2_cswap(c[1], c[2]); p2_cswap(c[3], c[4]); p2_cswap(c[5], c[6]);
-    // hull(c0): convex_hull's two monotone chains
-    P2* lo0 = L.lo0 + lane;
-    P2* up0 = L.up0 + lane;
-    int nl = 0, nu = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        while (nl >= 2 && cross2(lo0[(nl - 2) * 64], lo0[(nl - 1) * 64], c[i]) <= 0) nl--;
-        lo0[(nl++) * 64] = c[i];
-    }
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        while (nu >= 2 && cross2(up0[(nu - 2) * 64], up0[(nu - 1) * 64], c[i]) <= 0) nu--;
-        up0[(nu++) * 64] = c[i];
-    }
-    const int nl1 = nl - 1;
-    const int n0 = nl1 + (nu - 1);
-    // candidates
-    P2* cand = L.cand + lane;
-    int nc = 0;
-    bool slow = false;
-    for (int i = 0; i < n0; ++i) {
-        const P2 p = HULL_AT(lo0, up0, nl1, i);
-        if (point_in_polygon(p, ht, nt)) {
-            if (nc < FAST_CAND) cand[(nc++) * 64] = p;
-            else slow = true;
-        }
-    }
-    for (int i = 0; i < nt; ++i) {
-        // point_in_polygon(ht[i], h0, n0)
-        const P2 p = ht[i];
-        bool in = false;
-        for (int k = 0; k < n0; ++k) {
-            const P2 p1 = HULL_AT(lo0, up0, nl1, k);
-            const P2 p2 = HULL_AT(lo0, up0, nl1, (k + 1) % n0);
-            if ((p1.y > p.y) != (p2.y > p.y)) {
-                float xi = ((p.y - p1.y) * (p2.x - p1.x) / (p2.y - p1.y)) + p1.x;
-                if (p.x < xi) in = !in;
-            }
-        }
-        if (in) {
-            if (nc < FAST_CAND) cand[(nc++) * 64] = p;
-            else slow = true;
-        }
-    }
-    for (int i = 0; i < n0 && !slow; ++i) {
-        const P2 a1 = HULL_AT(lo0, up0, nl1, i);
-        const P2 a2 = HULL_AT(lo0, up0, nl1, (i + 1) % n0);
-        for (int j = 0; j < nt; ++j) {
-            const P2 b1 = ht[j], b2 = ht[(j + 1) % nt];
-            if (seg_boxes_apart(a1, a2, b1, b2)) continue;
-            P2 pt;
-            if (line_intersection(a1, a2, b1, b2, &pt)) {
-                if (nc < FAST_CAND) cand[(nc++) * 64] = pt;
-                else { slow = true; break; }
-            }
-        }
-    }
-    if (slow) {   // scratch path from the original corners (rare)
-        P2 cc[8];
-        for (int j = 0; j < 8; ++j) cc[j] = c0in[j];
-        return iou_hull_pre(cc, ht, nt, at, flags);
-    }
-    float a0 = 0.0f;
-    for (int i = 0; i < n0; ++i) {
-        const P2 p1 = HULL_AT(lo0, up0, nl1, i), p2 = HULL_AT(lo0, up0, nl1, (i + 1) % n0);
-        a0 += p1.x * p2.y - p2.x * p1.y;
-    }
-    a0 = (float)(fabs((double)a0) / 2.0);
-    // hull(cand): sort (insertion: same order as the exchange sort), upper chain into `up`,
-    // then the lower chain in place over the sorted candidates (it writes index <= i only)
-    for (int i = 1; i < nc; ++i) {
-        const P2 x = cand[i * 64];
-        int j = i - 1;
-        while (j >= 0 && p2_greater(cand[j * 64], x)) { cand[(j + 1) * 64] = cand[j * 64]; --j; }
-        cand[(j + 1) * 64] = x;
-    }
-    P2* up = L.up + lane;
-    int ni = 0, cl1 = 0;
-    if (nc > 0) {
-        int mu = 0;
-        for (int i = nc - 1; i >= 0; --i) {
-            const P2 x = cand[i * 64];
-            while (mu >= 2 && cross2(up[(mu - 2) * 64], up[(mu - 1) * 64], x) <= 0) mu--;
-            up[(mu++) * 64] = x;
-        }
-        int ml = 0;
-        for (int i = 0; i < nc; ++i) {
-            const P2 x = cand[i * 64];
-            while (ml >= 2 && cross2(cand[(ml - 2) * 64], cand[(ml - 1) * 64], x) <= 0) ml--;
-            cand[(ml++) * 64] = x;
-        }
-        cl1 = ml - 1;
-        ni = cl1 + (mu - 1);
-    }
-    if (ni > 8) *flags |= BF_DEV_HULL_OVERFLOW;
-    float inter = 0.0f;
-    for (int i = 0; i < ni; ++i) {
-        const P2 p1 = HULL_AT(cand, up, cl1, i), p2 = HULL_AT(cand, up, cl1, (i + 1) % ni);
-        inter += p1.x * p2.y - p2.x * p1.y;
-    }
-    inter = (float)(fabs((double)inter) / 2.0);
-    float uni = a0 + at - inter;
-    float iou = 0;
-    if (uni > 0) iou = (float)((double)inter / ((double)uni + 0.00001));
-    return iou;
-}
-
 // ------------------------------------------------------------------------------------------
-// Four lanes per (particle, view) pair (the refinement's terms kernel): the same IoU as
-// iou_hull_lds, with the pair's work split where it is independent.  Each lane projects two of
-// the eight corners; all four run the corner sort and hull(c0) (identical values on identical LDS
-// slots); the candidate tests (hull(c0) vertices in the target, target vertices in hull(c0), the
-// n0 x nt edge crossings) go round-robin over the four lanes and append to the pair's list with
-// an LDS atomic; the list is then ordered by rank (key (x, y), ties by list position -- equal keys
-// are equal points, so every arrival order gives the exchange sort's sequence) with each lane
-// ranking a quarter of it, and all four run the candidate hull's chains and the areas.  Every
-// arithmetic expression is the one iou_hull_lds evaluates, so the terms are bit-identical; the
-// dependent-LDS chain of one lane shrinks to the two hulls' monotone chains.
+// iou_hull_g4: iou_hull_pre for the refinement's terms kernel, four lanes per (particle, view)
+// pair, same arithmetic and bit-identical results.  iou_hull_pre keeps ~2 KB of per-thread arrays
+// (hull stacks, 64 candidates) that spill to scratch and are walked by one lane; here the pair's
+// stacks live in LDS, element e of pair `pr` at [e * G4_PAIRS + pr], and the work is split over
+// the four lanes where it is independent:
+//   - each lane projects two of the eight corners (k_fuse_terms); all four then sort the eight in
+//     registers by a 19-comparator network (any correct sort gives convex_hull's exchange-sort
+//     order: equal keys are equal points) and build hull(c0)'s two monotone chains (identical
+//     values on identical LDS slots);
+//   - the candidate tests (hull(c0) vertices in the target, target vertices in hull(c0), the
+//     n0 x nt edge crossings) go round-robin over the four lanes and append to the pair's list
+//     with an LDS atomic;
+//   - the list is ordered by rank (key (x, y), ties by list position -- equal keys are equal
+//     points, so every arrival order gives the exchange sort's sequence), each lane ranking a
+//     quarter of it, and all four run the candidate hull's chains and the areas.
+// Every arithmetic expression is the one iou_hull_pre evaluates; the dependent-LDS chain of one
+// lane shrinks to the two hulls' monotone chains.  A pair with more than FAST_CAND candidates
+// (never seen on real boxes: two convex 8-gons give at most 16 vertices + 16 crossings in general
+// position) runs iou_hull_pre itself from the original corners on its lane 0.
 // ------------------------------------------------------------------------------------------
+#ifndef FAST_CAND
+#define FAST_CAND 32   // (a diagnostic build lowers it to exercise the scratch fallback)
+#endif
 #define G4_PAIRS 16                      // pairs per one-wave workgroup
 struct HullG4 {
     P2 c0[8 * G4_PAIRS];                 // the projected corners, [j * 16 + pair]
@@ -329,6 +195,7 @@ struct HullG4 {
     P2 up[FAST_CAND * G4_PAIRS];         // upper chain of the candidate hull
     int cnt[G4_PAIRS];
 };
+// hull vertex i of a monotone-chain hull stored as lower[0..nl-1) ++ upper[0..nu-1)
 #define HULL_AT16(lo, up, nl1, i) ((i) < (nl1) ? (lo)[(i) * G4_PAIRS] : (up)[((i) - (nl1)) * G4_PAIRS])
 
 __device__ __forceinline__ bool p2_less(P2 a, P2 b) { return a.x < b.x || (a.x == b.x && a.y < b.y); }
@@ -467,6 +334,21 @@ struct FuseViews {
     float tc[FUSE_MAX_VIEWS][16];
 };
 
+// world corner c seen from the camera with pose P (4x4 row-major, camera to world): R^T (c - t),
+// pinhole projection, clamped to the image (compute_iou_value, box_fusion.py:347-361)
+__device__ __forceinline__ P2 project_corner(const float* c, const float* P, const bf_fuse_cfg& cfg) {
+    float vx = c[0] - P[3], vy = c[1] - P[7], vz = c[2] - P[11];
+    float cx = P[0] * vx + P[4] * vy + P[8] * vz;
+    float cy = P[1] * vx + P[5] * vy + P[9] * vz;
+    float cz = P[2] * vx + P[6] * vy + P[10] * vz;
+    float px = ((cx * cfg.K[0]) / cz + cfg.K[2]);
+    float py = ((cy * cfg.K[5]) / cz + cfg.K[6]);
+    P2 q;
+    q.x = (px > cfg.img_w) ? cfg.img_w : (px < 0) ? 0 : px;
+    q.y = (py > cfg.img_h) ? cfg.img_h : (py < 0) ? 0 : py;
+    return q;
+}
+
 // fitness of one particle (box already perturbed into its 8 corners) over all views
 __device__ float particle_fitness(const float* corners, const FuseViews& V, int nv,
                                   const bf_fuse_cfg& cfg, int* flags) {
@@ -475,14 +357,7 @@ __device__ float particle_fitness(const float* corners, const FuseViews& V, int 
         const float* P = V.pose[v];
         P2 c0[8], ct[8];
         for (int j = 0; j < 8; ++j) {
-            float vx = corners[3 * j] - P[3], vy = corners[3 * j + 1] - P[7], vz = corners[3 * j + 2] - P[11];
-            float cx = P[0] * vx + P[4] * vy + P[8] * vz;
-            float cy = P[1] * vx + P[5] * vy + P[9] * vz;
-            float cz = P[2] * vx + P[6] * vy + P[10] * vz;
-            float px = ((cx * cfg.K[0]) / cz + cfg.K[2]);
-            float py = ((cy * cfg.K[5]) / cz + cfg.K[6]);
-            c0[j].x = (px > cfg.img_w) ? cfg.img_w : (px < 0) ? 0 : px;
-            c0[j].y = (py > cfg.img_h) ? cfg.img_h : (py < 0) ? 0 : py;
+            c0[j] = project_corner(corners + 3 * j, P, cfg);
             ct[j].x = V.tc[v][2 * j];
             ct[j].y = V.tc[v][2 * j + 1];
         }
@@ -493,9 +368,10 @@ __device__ float particle_fitness(const float* corners, const FuseViews& V, int 
     return val / (cnt + 1e-6f);
 }
 
-// compute_iou_value's box perturbation + corners (box_fusion.py:289-331)
-__device__ __forceinline__ void particle_corners(const float* box, const float* R, const float* prow,
-                                                 const float* ss, float* corners) {
+// compute_iou_value's box perturbation (box_fusion.py:289-307): the particle's centre and its
+// sizes (l, h, w), floored at 0.01
+__device__ __forceinline__ void particle_dims(const float* box, const float* prow, const float* ss,
+                                              float* xyz, float* lhw) {
     float x = box[0] + prow[0] * ss[0];
     float y = box[1] + prow[1] * ss[1];
     float z = box[2] + prow[2] * ss[2];
@@ -505,7 +381,16 @@ __device__ __forceinline__ void particle_corners(const float* box, const float* 
     w = fmaxf(w, 0.01f);
     h = fmaxf(h, 0.01f);
     l = fmaxf(l, 0.01f);
-    const float xyz[3] = {x, y, z};
+    xyz[0] = x; xyz[1] = y; xyz[2] = z;
+    lhw[0] = l; lhw[1] = h; lhw[2] = w;
+}
+
+// ... and its 8 corners R v_c + xyz (box_fusion.py:310-331)
+__device__ __forceinline__ void particle_corners(const float* box, const float* R, const float* prow,
+                                                 const float* ss, float* corners) {
+    float xyz[3], lhw[3];
+    particle_dims(box, prow, ss, xyz, lhw);
+    const float l = lhw[0], h = lhw[1], w = lhw[2];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const float v[3] = {bf_vsign_x(c) > 0 ? l / 2 : -l / 2, bf_vsign_y(c) > 0 ? h / 2 : -h / 2,
@@ -666,7 +551,7 @@ __global__ void __launch_bounds__(64) k_fuse_targets(const float* __restrict__ v
     T.area = polygon_area(ht, nt);
 }
 
-#define TERM_THREADS 64   // one wave per workgroup (k_fuse_iter: its hull stacks take 40 KB of LDS)
+#define TERM_THREADS 64   // one wave per workgroup, with one HullG4 (15 KB of LDS)
 // one wave = G4_PAIRS (particle, view) pairs x 4 lanes (iou_hull_g4); the pairs of a workgroup
 // share the view (P % 64 == 0)
 __global__ void __launch_bounds__(TERM_THREADS) k_fuse_terms(const float* __restrict__ vpose,
@@ -691,29 +576,21 @@ __global__ void __launch_bounds__(TERM_THREADS) k_fuse_terms(const float* __rest
     if (lane < 16) s_pose[lane] = vpose[vi * 16 + lane];
     else if (lane < 16 + 18) reinterpret_cast<float*>(&s_th)[lane - 16] =
         reinterpret_cast<const float*>(th + (size_t)job * max_views + v)[lane - 16];
-    // this lane's two corners of the pair's particle box (particle_corners' expressions)
+    // this lane's two corners of the pair's particle box (particle_corners' expressions, written
+    // out: a per-corner helper called from here changes this kernel's instruction schedule)
     float b[6], r[9], ss[6];
     for (int k = 0; k < 6; ++k) { b[k] = S.box32[k]; ss[k] = S.ss[k]; }
     for (int k = 0; k < 9; ++k) r[k] = S.R[k];
-    const float* prow = pst + 6 * p;
-    float x = b[0] + prow[0] * ss[0];
-    float y = b[1] + prow[1] * ss[1];
-    float z = b[2] + prow[2] * ss[2];
-    float w = b[5] + prow[5] * ss[5];
-    float h = b[4] + prow[4] * ss[4];
-    float l = b[3] + prow[3] * ss[3];
-    w = fmaxf(w, 0.01f);
-    h = fmaxf(h, 0.01f);
-    l = fmaxf(l, 0.01f);
-    const float xyz[3] = {x, y, z};
+    float xyz[3], lhw[3];
+    particle_dims(b, pst + 6 * p, ss, xyz, lhw);
+    const float l = lhw[0], h = lhw[1], w = lhw[2];
     __syncthreads();
-    const float* Pm = s_pose;
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
         const int c = 2 * g + cc;
+        float cn[3];
         const float vv[3] = {bf_vsign_x(c) > 0 ? l / 2 : -l / 2, bf_vsign_y(c) > 0 ? h / 2 : -h / 2,
                              bf_vsign_z(c) > 0 ? w / 2 : -w / 2};
-        float cn[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             float sacc = 0.0f;
@@ -722,16 +599,7 @@ __global__ void __launch_bounds__(TERM_THREADS) k_fuse_terms(const float* __rest
             sacc += xyz[j];
             cn[j] = sacc;
         }
-        float vx = cn[0] - Pm[3], vy = cn[1] - Pm[7], vz = cn[2] - Pm[11];
-        float cx = Pm[0] * vx + Pm[4] * vy + Pm[8] * vz;
-        float cy = Pm[1] * vx + Pm[5] * vy + Pm[9] * vz;
-        float cz = Pm[2] * vx + Pm[6] * vy + Pm[10] * vz;
-        float px = ((cx * cfg.K[0]) / cz + cfg.K[2]);
-        float py = ((cy * cfg.K[5]) / cz + cfg.K[6]);
-        P2 q;
-        q.x = (px > cfg.img_w) ? cfg.img_w : (px < 0) ? 0 : px;
-        q.y = (py > cfg.img_h) ? cfg.img_h : (py < 0) ? 0 : py;
-        s_hull.c0[c * G4_PAIRS + pr] = q;
+        s_hull.c0[c * G4_PAIRS + pr] = project_corner(cn, s_pose, cfg);
     }
     __syncthreads();
     P2 c0[8];
@@ -752,11 +620,12 @@ struct StepLds {
 
 __device__ void fuse_step_body(int job, const float* __restrict__ pst, const bf_fuse_cfg& cfg,
                                FuseState* __restrict__ states, const float* __restrict__ terms,
-                               int max_views, int it, float* __restrict__ trace, StepLds& L) {
+                               int max_views, int it, float* __restrict__ trace) {
     const int t = threadIdx.x;
     const int P = cfg.pst_size;
     FuseState* G = states + job;
     if (G->stop) return;
+    __shared__ StepLds L;
     float* s_fit = L.fit;
     int* s_acc = L.acc;
     float* s_prod = L.prod;
@@ -885,80 +754,11 @@ __device__ void fuse_step_body(int job, const float* __restrict__ pst, const bf_
     }
 }
 
-// One launch per iteration: the terms of every (job, view, particle) as k_fuse_terms, then the
-// job's workgroup that finishes last (device-scope counter per job) runs the job's sequential
-// update — half the launches of the terms + step pair, on a path that is launch-latency bound.
-// The step reuses the hull stacks' LDS (dead by then).
-union IterLds {
-    HullLds hull;
-    StepLds step;
-};
-
-__global__ void __launch_bounds__(TERM_THREADS) k_fuse_iter(const float* __restrict__ vpose,
-                                                            const TargetHull* __restrict__ th,
-                                                            const float* __restrict__ pst,
-                                                            bf_fuse_cfg cfg,
-                                                            FuseState* __restrict__ states,
-                                                            float* __restrict__ terms, int max_views,
-                                                            int it, float* __restrict__ trace,
-                                                            int* __restrict__ done) {
-    __shared__ IterLds U;
-    __shared__ float s_pose[16];
-    __shared__ TargetHull s_th;
-    __shared__ int s_last;
-    const int job = blockIdx.y;
-    const FuseState& S = states[job];
-    const int P = cfg.pst_size;                           // multiple of 64
-    const int pair = blockIdx.x * TERM_THREADS + threadIdx.x;
-    const int v = pair / P, p = pair % P;                 // v uniform per (one-wave) workgroup
-    const int lane = threadIdx.x;
-    if (!S.stop && v < S.nv) {
-        const size_t vi = (size_t)S.off + v;
-        if (lane < 16) s_pose[lane] = vpose[vi * 16 + lane];
-        else if (lane < 16 + 18) reinterpret_cast<float*>(&s_th)[lane - 16] =
-            reinterpret_cast<const float*>(th + (size_t)job * max_views + v)[lane - 16];
-        __syncthreads();
-        float b[6], r[9], ss[6], corners[24];
-        for (int k = 0; k < 6; ++k) { b[k] = S.box32[k]; ss[k] = S.ss[k]; }
-        for (int k = 0; k < 9; ++k) r[k] = S.R[k];
-        particle_corners(b, r, pst + 6 * p, ss, corners);
-        const float* Pm = s_pose;
-        P2 c0[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float vx = corners[3 * j] - Pm[3], vy = corners[3 * j + 1] - Pm[7], vz = corners[3 * j + 2] - Pm[11];
-            float cx = Pm[0] * vx + Pm[4] * vy + Pm[8] * vz;
-            float cy = Pm[1] * vx + Pm[5] * vy + Pm[9] * vz;
-            float cz = Pm[2] * vx + Pm[6] * vy + Pm[10] * vz;
-            float px = ((cx * cfg.K[0]) / cz + cfg.K[2]);
-            float py = ((cy * cfg.K[5]) / cz + cfg.K[6]);
-            c0[j].x = (px > cfg.img_w) ? cfg.img_w : (px < 0) ? 0 : px;
-            c0[j].y = (py > cfg.img_h) ? cfg.img_h : (py < 0) ? 0 : py;
-        }
-        int flags = 0;
-        const float iou = iou_hull_lds(c0, s_th.h, s_th.n, s_th.area, U.hull, lane, &flags);
-        terms[((size_t)job * max_views + v) * P + p] = fabsf(1 - iou);
-        if (flags) atomicOr(&states[job].flags, flags);
-    }
-    // the job's last workgroup to finish runs the update
-    __threadfence();
-    __syncthreads();
-    if (lane == 0)
-        s_last = __hip_atomic_fetch_add(&done[job], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                 (int)gridDim.x - 1;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (lane == 0) done[job] = 0;                          // for the next iteration's launch
-    fuse_step_body(job, pst, cfg, states, terms, max_views, it, trace, U.step);
-}
-
 __global__ void __launch_bounds__(1024) k_fuse_step(const float* __restrict__ pst, bf_fuse_cfg cfg,
                                                     FuseState* __restrict__ states,
                                                     const float* __restrict__ terms, int max_views,
                                                     int it, float* __restrict__ trace) {
-    __shared__ StepLds L;
-    fuse_step_body(blockIdx.x, pst, cfg, states, terms, max_views, it, trace, L);
+    fuse_step_body(blockIdx.x, pst, cfg, states, terms, max_views, it, trace);
 }
 
 __global__ void __launch_bounds__(64) k_fuse_final(const FuseState* __restrict__ states, int n_jobs,
@@ -1006,11 +806,9 @@ static size_t fuse_targets_bytes(int n_jobs, int max_views) {
     return ((size_t)n_jobs * max_views * sizeof(TargetHull) + 255) & ~(size_t)255;
 }
 
-static size_t fuse_done_bytes(int n_jobs) { return ((size_t)n_jobs * sizeof(int) + 255) & ~(size_t)255; }
-
 BF_API size_t bf_fusion_fit_workspace_size(int n_jobs, int max_views, int pst_size) {
     if (n_jobs <= 0 || max_views <= 0 || pst_size <= 0) return 0;
-    return fuse_states_bytes(n_jobs) + fuse_targets_bytes(n_jobs, max_views) + fuse_done_bytes(n_jobs) +
+    return fuse_states_bytes(n_jobs) + fuse_targets_bytes(n_jobs, max_views) +
            (size_t)n_jobs * max_views * pst_size * sizeof(float);
 }
 
@@ -1032,25 +830,17 @@ BF_API int bf_fusion_fit(const int32_t* view_off, const int32_t* n_views, int n_
     FuseState* states = reinterpret_cast<FuseState*>(workspace);
     char* ws = reinterpret_cast<char*>(workspace) + fuse_states_bytes(n_jobs);
     TargetHull* th = reinterpret_cast<TargetHull*>(ws);
-    int* done = reinterpret_cast<int*>(ws + fuse_targets_bytes(n_jobs, max_views));
-    float* terms = reinterpret_cast<float*>(reinterpret_cast<char*>(done) + fuse_done_bytes(n_jobs));
-    if (hipMemsetAsync(done, 0, sizeof(int) * (size_t)n_jobs, s) != hipSuccess) return BF_ERR_LAUNCH;
+    float* terms = reinterpret_cast<float*>(ws + fuse_targets_bytes(n_jobs, max_views));
     const int P = cfg->pst_size;
     hipLaunchKernelGGL(k_fuse_init, dim3(n_jobs), dim3(64), 0, s, view_off, n_views, max_views,
                        view_box, view_R, view_score, *cfg, states);
     hipLaunchKernelGGL(k_fuse_targets, dim3(n_jobs), dim3(64), 0, s, view_tc, states, max_views, th);
-    const dim3 tgrid((unsigned)bf_cdiv(max_views * P, TERM_THREADS), (unsigned)n_jobs);
     const dim3 tgrid4((unsigned)bf_cdiv(max_views * P, G4_PAIRS), (unsigned)n_jobs);
     for (int it = 0; it < cfg->iters; ++it) {
-#if FUSE_SPLIT_ITER
         hipLaunchKernelGGL(k_fuse_terms, tgrid4, dim3(TERM_THREADS), 0, s, view_pose, th, pst,
                            *cfg, states, terms, max_views);
         hipLaunchKernelGGL(k_fuse_step, dim3(n_jobs), dim3(P), 0, s, pst, *cfg, states, terms,
                            max_views, it, trace);
-#else
-        hipLaunchKernelGGL(k_fuse_iter, tgrid, dim3(TERM_THREADS), 0, s, view_pose, th, pst, *cfg,
-                           states, terms, max_views, it, trace, done);
-#endif
     }
     hipLaunchKernelGGL(k_fuse_final, dim3(bf_cdiv(n_jobs, 64)), dim3(64), 0, s, states, n_jobs,
                        out_box, out_updated, out_iters, status);

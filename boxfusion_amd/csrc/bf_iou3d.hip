@@ -9,12 +9,12 @@
 // unit outward normal in f64 from the f32 corners) — verified bit-exact against scipy/qhull on
 // the golden pairs.
 //
-// Layout: k_obb_prep writes per-box planes (12 x f64[4]) and gate points (20 x f32[3]) to the
-// workspace; k_obb_pairs runs one 256-thread workgroup per unordered pair (i<j): the gate is one
-// wave-wide ballot, the grid is 15625 points striped over 256 lanes (f64 VALU, no MFMA).
+// Layout: four launches per matrix, all f64 VALU (no MFMA).  k_obb_prep writes per-box planes
+// (12 x f64[4]), gate points (20 x f32[3]) and the f32 AABB to the workspace, the matrix diagonal,
+// and resets the work list; k_obb_gate runs the gate of every unordered pair (i<j), one wave per
+// pair, writes IoU 0 for the pairs it rejects and lists the others; k_obb_cols counts the grid of
+// the listed pairs, one lane per (ix, iy) column of 25 z points; k_obb_final divides.
 #include "bf_common.h"
-
-#define IOU_THREADS 256
 
 __constant__ int c_face[6][4] = {{0, 3, 7, 4}, {1, 2, 6, 5}, {0, 1, 5, 4},
                                  {3, 2, 6, 7}, {0, 1, 2, 3}, {4, 5, 6, 7}};
@@ -28,11 +28,10 @@ struct BoxPrep {
     float pad[2];
 };
 
-// device-side work list of the split form (k_obb_gate / k_obb_grid)
+// header of the device-side work list (k_obb_gate appends, k_obb_cols / k_obb_final read)
 struct ObbWork {
     int n_gated;      // pairs that passed the gate
-    int grid_done;    // k_obb_grid workgroups finished (the last one divides)
-    int pad[2];
+    int pad[3];       // (k_obb_prep clears pad[0] along with n_gated: one 8-byte store)
 };
 
 __device__ void tri_plane(const double* p0, const double* p1, const double* p2, const double* cen,
@@ -56,7 +55,7 @@ __global__ void __launch_bounds__(64) k_obb_prep(const float* __restrict__ corne
                                                  BoxPrep* __restrict__ prep, double* __restrict__ iou,
                                                  ObbWork* __restrict__ w) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t == 0 && w) { w->n_gated = 0; w->grid_done = 0; }
+    if (t == 0 && w) { w->n_gated = 0; w->pad[0] = 0; }
     const int i = t >> 3, sub = t & 7;
     if (i >= n) return;
     const float* c = corners + 24 * i;
@@ -123,114 +122,22 @@ __device__ __forceinline__ void pair_of(long long p, int n, int* i, int* j) {
     *j = (int)(p - start(r) + r + 1);
 }
 
-__global__ void __launch_bounds__(IOU_THREADS) k_obb_pairs(const BoxPrep* __restrict__ prep, int n,
-                                                           double* __restrict__ iou) {
-    int i, j;
-    pair_of((long long)blockIdx.x, n, &i, &j);
-    __shared__ double pl[2][12][4];
-    __shared__ double g[3][25];
-    __shared__ int s_gate;
-    __shared__ long long s_red[3][IOU_THREADS / 64];
-    const int t = threadIdx.x;
-    const BoxPrep& A = prep[i];
-    const BoxPrep& B = prep[j];
-    if (t < 48) pl[0][t >> 2][t & 3] = A.pl[t >> 2][t & 3];
-    else if (t < 96) pl[1][(t - 48) >> 2][(t - 48) & 3] = B.pl[(t - 48) >> 2][(t - 48) & 3];
-    if (t == 0) s_gate = 0;
-    __syncthreads();
-    // gate: lanes 0..19 test A's points against B, lanes 20..39 B's against A (first wave)
-    if (t < 64) {
-        bool in = false;
-        if (t < 20) in = inside12(A.pt[t][0], A.pt[t][1], A.pt[t][2], pl[1]);
-        else if (t < 40) in = inside12(B.pt[t - 20][0], B.pt[t - 20][1], B.pt[t - 20][2], pl[0]);
-        unsigned long long m = __ballot(in);
-        if (t == 0) s_gate = (m != 0ull) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_gate) {
-        if (t == 0) {
-            iou[(size_t)i * n + j] = 0.0;
-            iou[(size_t)j * n + i] = 0.0;
-        }
-        return;
-    }
-    // numpy.linspace(f64(min), f64(max), 25) per axis over the union AABB
-    if (t < 75) {
-        int ax = t / 25, k = t % 25;
-        float lo = fminf(A.mn[ax], B.mn[ax]);
-        float hi = fmaxf(A.mx[ax], B.mx[ax]);
-        double start = lo, stop = hi;
-        double step = (stop - start) / 24.0;
-        g[ax][k] = (k == 24) ? stop : (double)k * step + start;
-    }
-    __syncthreads();
-    // A grid point more than 1e-3 outside a box's (f32) AABB is outside its hull: some facet plane
-    // is then at a signed distance >= 1e-3/sqrt(3) >> the 1e-6 tolerance, so skipping the 12
-    // f64 plane tests there changes no count (the tests themselves are unchanged).
-    const double m = 1e-3;
-    const double alo0 = A.mn[0] - m, alo1 = A.mn[1] - m, alo2 = A.mn[2] - m;
-    const double ahi0 = A.mx[0] + m, ahi1 = A.mx[1] + m, ahi2 = A.mx[2] + m;
-    const double blo0 = B.mn[0] - m, blo1 = B.mn[1] - m, blo2 = B.mn[2] - m;
-    const double bhi0 = B.mx[0] + m, bhi1 = B.mx[1] + m, bhi2 = B.mx[2] + m;
-    // both plane sets in registers (96 f64): read from LDS once, not 96 broadcast reads per point
-    double pa[12][4], pb[12][4];
-#pragma unroll
-    for (int k = 0; k < 12; ++k)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { pa[k][c] = pl[0][k][c]; pb[k][c] = pl[1][k][c]; }
-    long long n1 = 0, n2 = 0, n12 = 0;
-    for (int p = t; p < 15625; p += IOU_THREADS) {
-        int ix = p / 625, iy = (p / 25) % 25, iz = p % 25;
-        double x = g[0][ix], y = g[1][iy], z = g[2][iz];
-        const bool ina = x >= alo0 && x <= ahi0 && y >= alo1 && y <= ahi1 && z >= alo2 && z <= ahi2;
-        const bool inb = x >= blo0 && x <= bhi0 && y >= blo1 && y <= bhi1 && z >= blo2 && z <= bhi2;
-        bool a = ina && inside12(x, y, z, pa);
-        bool b = inb && inside12(x, y, z, pb);
-        n1 += a;
-        n2 += b;
-        n12 += (a && b);
-    }
-    n1 = bf_wave_sum_i64(n1);
-    n2 = bf_wave_sum_i64(n2);
-    n12 = bf_wave_sum_i64(n12);
-    if (bf_lane() == 0) {
-        s_red[0][t >> 6] = n1;
-        s_red[1][t >> 6] = n2;
-        s_red[2][t >> 6] = n12;
-    }
-    __syncthreads();
-    if (t == 0) {
-        long long a = 0, b = 0, c = 0;
-        for (int w = 0; w < IOU_THREADS / 64; ++w) { a += s_red[0][w]; b += s_red[1][w]; c += s_red[2][w]; }
-        double v = (double)c / ((double)(a + b - c) + 1e-6);
-        iou[(size_t)i * n + j] = v;
-        iou[(size_t)j * n + i] = v;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
-// Split form (default): the gate and the grid count are separate launches, so the grid count
-// only runs for the pairs that pass the gate and spreads each over OBB_SPLIT workgroups.  One
-// workgroup per pair (k_obb_pairs above) leaves most of the chip idle behind a few long
-// workgroups and, on the fusion stream's CU partition, queues thousands of short ones.
+// The gate and the grid count are separate launches, so the grid count only runs for the pairs
+// that pass the gate and each such pair spreads over several waves.  (One workgroup per pair
+// leaves most of the chip idle behind a few long workgroups and, on the fusion stream's CU
+// partition, queues thousands of short ones.)
 //   k_obb_gate   one wave per pair: 40-lane gate ballot; IoU 0 written for gated-out pairs,
-//                the others appended to a device list (order-free: each pair owns its entries)
-//   k_obb_grid   persistent: item = (gated pair, split), 15625 / OBB_SPLIT grid points each,
-//                integer counts added atomically (exact, order-free)
-//                the last workgroup to finish divides: IoU = n12 / ((n1 + n2 - n12) + 1e-6)
-//   (k_obb_prep also writes the diagonal and resets the work list: 3 launches per matrix)
+//                the others appended to a device list with their three counts zeroed
+//                (order-free: each pair owns its entries)
+//   k_obb_cols   persistent: item = (gated pair, 64-column chunk), one wave each; integer
+//                counts added atomically (exact, order-free)
+//   k_obb_final  one lane per gated pair: IoU = n12 / ((n1 + n2 - n12) + 1e-6).  Its own
+//                launch: a last-workgroup-divides tail in the count kernel saves the launch but
+//                makes every workgroup's release fence write back L2, which costs more under
+//                the detect load.
 // ------------------------------------------------------------------------------------------
-#ifndef OBB_SPLIT
-#define OBB_SPLIT 2         // (a diagnostic build sets 0: one workgroup per pair, k_obb_pairs)
-#endif
 #define OBB_GRID_WGS 512
-#ifndef OBB_LAST_BLOCK
-// 0 (default): the division as its own launch (k_obb_final); 1 (diagnostic build): the grid's
-// last workgroup divides (one launch less, but every workgroup's release fence writes back L2,
-// which costs more than the launch under the detect load)
-#define OBB_LAST_BLOCK 0
-#endif
-
 
 __global__ void __launch_bounds__(256) k_obb_gate(const BoxPrep* __restrict__ prep, int n,
                                                   long long pairs, double* __restrict__ iou,
@@ -261,113 +168,21 @@ __global__ void __launch_bounds__(256) k_obb_gate(const BoxPrep* __restrict__ pr
     }
 }
 
-__global__ void __launch_bounds__(IOU_THREADS) k_obb_grid(const BoxPrep* __restrict__ prep, int n,
-                                                          ObbWork* __restrict__ w,
-                                                          const int* __restrict__ gated,
-                                                          int* __restrict__ cnt,
-                                                          double* __restrict__ iou) {
-    __shared__ double pl[2][12][4];
-    __shared__ double g[3][25];
-    __shared__ int s_red[3][IOU_THREADS / 64];
-    const int t = threadIdx.x;
-    constexpr int SPLIT = OBB_SPLIT > 0 ? OBB_SPLIT : 1;
-    const int items = w->n_gated * SPLIT;
-    constexpr int PER = (15625 + SPLIT - 1) / SPLIT;
-    for (int it = blockIdx.x; it < items; it += gridDim.x) {
-        const int slot = it / SPLIT, part = it % SPLIT;
-        int i, j;
-        pair_of((long long)gated[slot], n, &i, &j);
-        const BoxPrep& A = prep[i];
-        const BoxPrep& B = prep[j];
-        __syncthreads();                                     // previous item's LDS reads done
-        if (t < 48) pl[0][t >> 2][t & 3] = A.pl[t >> 2][t & 3];
-        else if (t < 96) pl[1][(t - 48) >> 2][(t - 48) & 3] = B.pl[(t - 48) >> 2][(t - 48) & 3];
-        else if (t < 96 + 75) {
-            // numpy.linspace(f64(min), f64(max), 25) per axis over the union AABB
-            const int ax = (t - 96) / 25, k = (t - 96) % 25;
-            float lo = fminf(A.mn[ax], B.mn[ax]);
-            float hi = fmaxf(A.mx[ax], B.mx[ax]);
-            double start = lo, stop = hi;
-            double step = (stop - start) / 24.0;
-            g[ax][k] = (k == 24) ? stop : (double)k * step + start;
-        }
-        __syncthreads();
-        // points outside a box's AABB by > 1e-3 skip its plane tests (see k_obb_pairs)
-        const double m = 1e-3;
-        const double alo0 = A.mn[0] - m, alo1 = A.mn[1] - m, alo2 = A.mn[2] - m;
-        const double ahi0 = A.mx[0] + m, ahi1 = A.mx[1] + m, ahi2 = A.mx[2] + m;
-        const double blo0 = B.mn[0] - m, blo1 = B.mn[1] - m, blo2 = B.mn[2] - m;
-        const double bhi0 = B.mx[0] + m, bhi1 = B.mx[1] + m, bhi2 = B.mx[2] + m;
-        int n1 = 0, n2 = 0, n12 = 0;
-        const int p0 = part * PER, p1 = min(p0 + PER, 15625);
-        for (int p = p0 + t; p < p1; p += IOU_THREADS) {
-            int ix = p / 625, iy = (p / 25) % 25, iz = p % 25;
-            double x = g[0][ix], y = g[1][iy], z = g[2][iz];
-            const bool ina = x >= alo0 && x <= ahi0 && y >= alo1 && y <= ahi1 && z >= alo2 && z <= ahi2;
-            const bool inb = x >= blo0 && x <= bhi0 && y >= blo1 && y <= bhi1 && z >= blo2 && z <= bhi2;
-            bool a = ina && inside12(x, y, z, pl[0]);
-            bool b = inb && inside12(x, y, z, pl[1]);
-            n1 += a;
-            n2 += b;
-            n12 += (a && b);
-        }
-        n1 = bf_wave_sum_i32(n1);
-        n2 = bf_wave_sum_i32(n2);
-        n12 = bf_wave_sum_i32(n12);
-        if (bf_lane() == 0) {
-            s_red[0][t >> 6] = n1;
-            s_red[1][t >> 6] = n2;
-            s_red[2][t >> 6] = n12;
-        }
-        __syncthreads();
-        if (t < 3) {
-            int s = 0;
-            for (int q = 0; q < IOU_THREADS / 64; ++q) s += s_red[t][q];
-            atomicAdd(&cnt[3 * slot + t], s);
-        }
-    }
-    if (!OBB_LAST_BLOCK) return;
-    // the last workgroup to finish divides: IoU = n12 / ((n1 + n2 - n12) + 1e-6)
-    __shared__ int s_last;
-    __threadfence();
-    __syncthreads();
-    if (t == 0)
-        s_last = __hip_atomic_fetch_add(&w->grid_done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                 (int)gridDim.x - 1;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    const int ng = __hip_atomic_load(&w->n_gated, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int slot = t; slot < ng; slot += IOU_THREADS) {
-        int i, j;
-        pair_of((long long)gated[slot], n, &i, &j);
-        const long long a = __hip_atomic_load(&cnt[3 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const long long b = __hip_atomic_load(&cnt[3 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const long long c = __hip_atomic_load(&cnt[3 * slot + 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double v = (double)c / ((double)(a + b - c) + 1e-6);
-        iou[(size_t)i * n + j] = v;
-        iou[(size_t)j * n + i] = v;
-    }
-}
-
-
-
-
 // ------------------------------------------------------------------------------------------
-// Column form (default, OBB_COLS 1): one lane per grid column (ix, iy), 25 z points each.
+// Grid count by columns: one lane per grid column (ix, iy), 25 z points each.
 // Along a column x, y and the plane's partial sum S = x*a + y*b are fixed, z_k = linspace(k) is
 // non-decreasing in k, and v(k) = (S + z_k*c) + d is a chain of monotone roundings of z_k*c, so
 // the test v <= 1e-6 holds on a prefix of k (c > 0), a suffix (c < 0) or all / none (c == 0 or
 // NaN: v does not depend on z).  Each of the 12 plane tests is therefore a 5-step binary search
 // for its boundary and the box's inside set on the column is the interval they cut out,
-// intersected with the AABB cull's interval (the same two monotone z tests the point form
-// makes).  Counts: n1 = |I_A|, n2 = |I_B|, n12 = |I_A ∩ I_B| — the point form's counts exactly,
-// in ≈ 140 instead of ≈ 25·12·3 f64 operations per column and box.  A pair whose z step is not
-// >= 0 or whose planes are not all finite takes the point-by-point loop over its 25 z values.
+// intersected with the AABB cull's interval (two more monotone z tests).  Counts: n1 = |I_A|,
+// n2 = |I_B|, n12 = |I_A ∩ I_B| — exactly what testing the 25 points one by one counts, in ≈ 140
+// instead of ≈ 25·12·3 f64 operations per column and box.  A pair whose z step is not >= 0 or
+// whose planes are not all finite takes the point-by-point loop over its 25 z values.
+// AABB cull (both paths): a grid point more than 1e-3 outside a box's (f32) AABB is outside its
+// hull: some facet plane is then at a signed distance >= 1e-3/sqrt(3) >> the 1e-6 tolerance, so
+// skipping the 12 f64 plane tests there changes no count (the tests themselves are unchanged).
 // ------------------------------------------------------------------------------------------
-#ifndef OBB_COLS
-#define OBB_COLS 1
-#endif
 #define OBB_COL_CHUNKS 10          // 64-column chunks per pair (625 columns)
 
 struct ZLine {
@@ -440,7 +255,7 @@ __global__ void __launch_bounds__(256) k_obb_cols(const BoxPrep* __restrict__ pr
         pair_of((long long)gated[slot], n, &i, &j);
         const BoxPrep& A = prep[i];
         const BoxPrep& B = prep[j];
-        // numpy.linspace(f64(min), f64(max), 25) per axis over the union AABB (as k_obb_grid)
+        // numpy.linspace(f64(min), f64(max), 25) per axis over the union AABB 
         const ZLine gx{(double)fminf(A.mn[0], B.mn[0]), 0.0, (double)fmaxf(A.mx[0], B.mx[0])};
         const ZLine gy{(double)fminf(A.mn[1], B.mn[1]), 0.0, (double)fmaxf(A.mx[1], B.mx[1])};
         ZLine gz{(double)fminf(A.mn[2], B.mn[2]), 0.0, (double)fmaxf(A.mx[2], B.mx[2])};
@@ -524,25 +339,13 @@ BF_API int bf_obb_iou_matrix(const float* corners, int n, double* iou, void* wor
     if (pairs > 0x7fffffffLL / 4) return BF_ERR_CAPACITY;
     hipLaunchKernelGGL(k_obb_prep, dim3(bf_cdiv(8 * n, 64)), dim3(64), 0, s, corners, n, prep, iou, w);
     if (pairs > 0) {
-        if (OBB_SPLIT == 0) {
-            hipLaunchKernelGGL(k_obb_pairs, dim3((unsigned)pairs), dim3(IOU_THREADS), 0, s, prep, n, iou);
-        } else {
-            hipLaunchKernelGGL(k_obb_gate, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, prep, n,
-                               pairs, iou, w, gated, cnt);
-            if (OBB_COLS) {
-                const long long waves = pairs * OBB_COL_CHUNKS;
-                const unsigned gw = (unsigned)std::min<long long>((waves + 3) / 4, OBB_GRID_WGS);
-                hipLaunchKernelGGL(k_obb_cols, dim3(gw), dim3(256), 0, s, prep, n, w, gated, cnt);
-            } else {
-                const unsigned gw = (unsigned)(pairs * (OBB_SPLIT > 0 ? OBB_SPLIT : 1) < OBB_GRID_WGS
-                                                   ? pairs * (OBB_SPLIT > 0 ? OBB_SPLIT : 1) : OBB_GRID_WGS);
-                hipLaunchKernelGGL(k_obb_grid, dim3(gw), dim3(IOU_THREADS), 0, s, prep, n, w, gated, cnt,
-                                   iou);
-            }
-            if (OBB_COLS || !OBB_LAST_BLOCK)
-                hipLaunchKernelGGL(k_obb_final, dim3(bf_cdiv((unsigned)pairs, 256)), dim3(256), 0, s, n,
-                                   w, gated, cnt, iou);
-        }
+        hipLaunchKernelGGL(k_obb_gate, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, prep, n,
+                           pairs, iou, w, gated, cnt);
+        const long long waves = pairs * OBB_COL_CHUNKS;
+        const unsigned gw = (unsigned)std::min<long long>((waves + 3) / 4, OBB_GRID_WGS);
+        hipLaunchKernelGGL(k_obb_cols, dim3(gw), dim3(256), 0, s, prep, n, w, gated, cnt);
+        hipLaunchKernelGGL(k_obb_final, dim3(bf_cdiv((unsigned)pairs, 256)), dim3(256), 0, s, n, w,
+                           gated, cnt, iou);
     }
     return bf_check_launch();
 }
