@@ -1246,6 +1246,54 @@ def cloud_extract(table):
     return key, count, sums, n
 
 
+# ------------------------------------------------------------------------------------------
+# evaluation against ground truth (bf_eval.hip; f64 throughout, off the timed path)
+# ------------------------------------------------------------------------------------------
+def _f64_rows(t, tail, name):
+    t = _need(t, torch.float64, name).contiguous()
+    if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tuple(tail):
+        raise HipError(f"{name}: expected [n,{','.join(map(str, tail))}], got {tuple(t.shape)}")
+    return t
+
+
+def gt_frustum_seen(corners, pose_inv, fx, fy, cx, cy, W, H, near, far):
+    """bf_gt_frustum: corners f64 [N,8,3] (world), pose_inv f64 [M,4,4] -> seen u8 [N,8], 1 where the
+    corner projects into at least one frame (filter_gt_boxes.py:24-62)"""
+    corners = _f64_rows(corners, (8, 3), "gt_frustum_seen: corners")
+    pose_inv = _f64_rows(pose_inv, (4, 4), "gt_frustum_seen: pose_inv")
+    n, m = corners.shape[0], pose_inv.shape[0]
+    seen = torch.zeros((n, 8), dtype=torch.uint8, device=corners.device)
+    _check(lib().bf_gt_frustum(_ptr(corners), c_int(n), _ptr(pose_inv), c_int(m), c_double(fx), c_double(fy),
+                               c_double(cx), c_double(cy), c_int(int(W)), c_int(int(H)), c_double(near),
+                               c_double(far), _ptr(seen), _stream()), "bf_gt_frustum")
+    return seen
+
+
+def nn_min_dist2(query, points):
+    """bf_nn_min_dist2: query f64 [Q,3], points f64 [P,3] -> d2 f64 [Q], the squared distance to the
+    nearest point (+inf when P == 0)"""
+    query = _f64_rows(query, (3,), "nn_min_dist2: query")
+    points = _f64_rows(points, (3,), "nn_min_dist2: points")
+    q, p = query.shape[0], points.shape[0]
+    d2 = torch.full((q,), float("inf"), dtype=torch.float64, device=query.device)
+    _check(lib().bf_nn_min_dist2(_ptr(query), c_int(q), _ptr(points), ctypes.c_longlong(p), _ptr(d2), _stream()),
+           "bf_nn_min_dist2")
+    return d2
+
+
+def obb_iou_exact(a, b, with_inter=False):
+    """bf_obb_iou_exact: a f64 [P,12], b f64 [G,12] (centre, three half-axis vectors) -> iou f64
+    [P,G], and the intersection volumes f64 [P,G] when with_inter"""
+    a = _f64_rows(a, (12,), "obb_iou_exact: a")
+    b = _f64_rows(b, (12,), "obb_iou_exact: b")
+    p, g = a.shape[0], b.shape[0]
+    iou = torch.empty((p, g), dtype=torch.float64, device=a.device)
+    inter = torch.empty((p, g), dtype=torch.float64, device=a.device) if with_inter else None
+    _check(lib().bf_obb_iou_exact(_ptr(a), c_int(p), _ptr(b), c_int(g), _ptr(iou), _ptr(inter), _stream()),
+           "bf_obb_iou_exact")
+    return (iou, inter) if with_inter else iou
+
+
 FP8 = torch.float8_e4m3fn      # OCP e4m3 (gfx950's fp8; not the MI300 fnuz variant)
 FP8_MAX = 448.0
 _FP8_OUT = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}

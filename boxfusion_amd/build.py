@@ -31,6 +31,7 @@ SOURCES = {
     "bf_jpeg.hip": EXACT,
     "bf_fseq.hip": EXACT,
     "bf_cloud.hip": EXACT,
+    "bf_eval.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 

@@ -761,6 +761,41 @@ size_t bf_jpeg_workspace_bytes(int F, int H, int W);
 int bf_jpeg_decode_rgb(const uint8_t* files, const int64_t* offsets, int F, int H, int W, uint8_t* rgb,
                        void* work, size_t work_bytes, int32_t* status, void* stream);
 
+/* ---- evaluation against ground truth (reference: data_process/filter_gt_boxes.py; off the timed
+ * path, every value f64) ----
+ * bf_gt_frustum restates frustum_culling_bbox_level (filter_gt_boxes.py:24-68) up to its per-corner
+ * mask: corners f64 [N,8,3] in the world frame, pose_inv f64 [M,4,4] = np.linalg.inv(pose) computed
+ * by the host as :40 does, so both sides start from the same values.  Corner c is seen in frame m when
+ *   z > z_near && z < z_far                      (:50, both strict)
+ *   u = (int)(fx x / z + cx), 0 <= u < W         (:53, :57; the cast truncates toward zero, so u in
+ *   v = (int)(fy y / z + cy), 0 <= v < H          (-1, 0) counts as inside)
+ * with (x, y, z) = pose_inv[m] (corner, 1) (:42-47); u and v are looked at only where the z test
+ * passed, and a pose holding inf or nan makes every comparison false (a lost-tracking pose shows
+ * nothing and raises nothing).  seen u8 [N,8] is zeroed by the caller; the kernel only stores 1.  The
+ * host finishes with seen.sum(1) >= 6 (:65-66). */
+int bf_gt_frustum(const double* corners, int N, const double* pose_inv, int M, double fx, double fy,
+                  double cx, double cy, int W, int H, double z_near, double z_far, uint8_t* seen,
+                  void* stream);
+/* bf_nn_min_dist2: d2[q] = min over points of (dx dx + dy dy) + dz dz for query f64 [Q,3] and points
+ * f64 [P,3], the square of what KDTree.query(bbox, k=1) returns (filter_gt_boxes.py:79-84).  d2 f64
+ * [Q] is filled with +inf by the caller and lowered with 64-bit unsigned atomic minima on the bit
+ * pattern, so the result is the same bits whatever order the blocks arrive in.  The host takes the
+ * sqrt, compares < threshold and keeps a box with >= 4 near corners (:86-90). */
+int bf_nn_min_dist2(const double* query, int Q, const double* points, long long P, double* d2,
+                    void* stream);
+/* bf_obb_iou_exact: the true volume of the intersection of two oriented boxes and their IoU (the
+ * reference releases no evaluation code; bf_obb_iou_matrix above is its association IoU, a 25^3
+ * sample grid behind a vertex gate, which is right for NMS and too coarse for a metric).  a f64
+ * [P,12], b f64 [G,12]: a row is a centre and three half-axis vectors.  iou f64 [P,G]; inter f64
+ * [P,G] (the volume) may be NULL.  Pairs apart along one of the six face normals give exactly 0
+ * (face-to-face touching included), as does a box with a zero half-axis.  Otherwise the twelve face
+ * quads are clipped by the other box's half-spaces and summed by the divergence theorem, with
+ * eps = 1e-12 x the larger half-diagonal: a vertex is inside a half-space when its signed distance
+ * is <= eps, and a face of b lying within eps of a face plane of a with the same outward side is
+ * left to a's face.  0 <= inter <= min(vol a, vol b) always holds. */
+int bf_obb_iou_exact(const double* a, int P, const double* b, int G, double* iou, double* inter,
+                     void* stream);
+
 /* placement probe (diagnostic): n_wg workgroups on `stream`, each spinning `spin` cycles, write
  * out[2b] = HW_ID (CU bits 11:8, SH 12, SE 15:13) and out[2b+1] = XCC id -- which CUs a (CU-masked)
  * stream really runs on */
