@@ -1247,6 +1247,108 @@ def cloud_extract(table):
 
 
 # ------------------------------------------------------------------------------------------
+# headless renderer (bf_render.hip)
+# ------------------------------------------------------------------------------------------
+def _render_target(name, keys):
+    """(V, H, W) of a key buffer int64 [V,H,W] holding the uint64 keys"""
+    _need(keys, torch.int64, f"{name}: keys")
+    if keys.dim() != 3:
+        raise HipError(f"{name}: keys [V,H,W], got {tuple(keys.shape)}")
+    return tuple(int(s) for s in keys.shape)
+
+
+def _render_cams(name, cams, V, intr):
+    cams = _need(cams, torch.float32, f"{name}: cams").contiguous()
+    if tuple(cams.shape) != (V, 12):
+        raise HipError(f"{name}: cams [{V},12] (R row-major, t), got {tuple(cams.shape)}")
+    fx, fy, cx, cy = (c_float(float(v)) for v in intr)
+    return cams, (fx, fy, cx, cy)
+
+
+def render_clear(keys):
+    """every key of keys int64 [V,H,W] to empty (bf_render_clear)"""
+    V, H, W = _render_target("render_clear", keys)
+    _check(lib().bf_render_clear(_ptr(keys), c_int(V), c_int(H), c_int(W), _stream()), "bf_render_clear")
+
+
+def _render_points_work(keys, xyz, rgb, cams, intr, near, far, radius, layer, stats=None):
+    n, V = int(xyz.shape[0]), int(keys.shape[0])
+    # algorithmic bytes: the points once per view, one 8-byte key per splat pixel
+    return (dict(kind="render_points", n=n, views=V, radius=int(radius)), 0.0,
+            float(n) * V * (15 + 8 * (2 * int(radius) + 1) ** 2))
+
+
+@_timed(_render_points_work)
+def render_points(keys, xyz, rgb, cams, intr, near, far, radius, layer, stats=None):
+    """xyz f32 [n,3] / rgb u8 [n,3] into keys int64 [V,H,W] (bf_render_points); cams f32 [V,12], intr
+    (fx, fy, cx, cy); stats: None or int64 [2] added to (pixels offered, atomics issued)"""
+    V, H, W = _render_target("render_points", keys)
+    xyz = _need(xyz, torch.float32, "render_points: xyz").contiguous()
+    rgb = _need(rgb, torch.uint8, "render_points: rgb").contiguous()
+    n = xyz.shape[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != (n, 3):
+        raise HipError(f"render_points: xyz [n,3] and rgb [n,3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+    if stats is not None and (_need(stats, torch.int64, "render_points: stats").numel() < 2):
+        raise HipError("render_points: stats int64 [2]")
+    cams, (fx, fy, cx, cy) = _render_cams("render_points", cams, V, intr)
+    _check(lib().bf_render_points(_ptr(xyz), _ptr(rgb), ctypes.c_longlong(n), _ptr(cams), c_int(V), fx, fy, cx, cy,
+                                  c_int(H), c_int(W), c_float(float(near)), c_float(float(far)), c_int(int(radius)),
+                                  c_int(int(layer)), _ptr(keys), _ptr(stats), _stream()), "bf_render_points")
+
+
+def _render_edges_work(keys, corners, colors, mask, cams, intr, near, half_width, layer):
+    b, V = int(corners.shape[0]), int(keys.shape[0])
+    return dict(kind="render_edges", boxes=b, views=V, half_width=int(half_width)), 0.0, float(b) * V * (96 + 3)
+
+
+@_timed(_render_edges_work)
+def render_edges(keys, corners, colors, mask, cams, intr, near, half_width, layer):
+    """the wireframes of corners f32 [B,8,3] in colors u8 [B,3] (mask: None or u8 / bool [B]) into
+    keys int64 [V,H,W] (bf_render_edges)"""
+    V, H, W = _render_target("render_edges", keys)
+    corners = _need(corners, torch.float32, "render_edges: corners").contiguous()
+    colors = _need(colors, torch.uint8, "render_edges: colors").contiguous()
+    b = corners.shape[0]
+    if tuple(corners.shape) != (b, 8, 3) or tuple(colors.shape) != (b, 3):
+        raise HipError(f"render_edges: corners [B,8,3] and colors [B,3], got {tuple(corners.shape)} and {tuple(colors.shape)}")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.contiguous().view(torch.uint8)
+        mask = _need(mask, torch.uint8, "render_edges: mask").contiguous()
+        if tuple(mask.shape) != (b,):
+            raise HipError(f"render_edges: mask [{b}], got {tuple(mask.shape)}")
+    cams, (fx, fy, cx, cy) = _render_cams("render_edges", cams, V, intr)
+    _check(lib().bf_render_edges(_ptr(corners), _ptr(colors), _ptr(mask), c_int(b), _ptr(cams), c_int(V), fx, fy, cx, cy,
+                                 c_int(H), c_int(W), c_float(float(near)), c_int(int(half_width)), c_int(int(layer)),
+                                 _ptr(keys), _stream()), "bf_render_edges")
+
+
+def _render_resolve_work(keys, background=(0, 0, 0)):
+    return dict(kind="render_resolve", pixels=int(keys.numel())), 0.0, float(keys.numel()) * (8 + 3 + 4)
+
+
+@_timed(_render_resolve_work)
+def render_resolve(keys, background=(0, 0, 0)):
+    """keys int64 [V,H,W] -> (rgb u8 [V,H,W,3], depth f32 [V,H,W]) (bf_render_resolve); background:
+    an (r, g, b) constant or a u8 image [V,H,W,3] for the empty pixels"""
+    V, H, W = _render_target("render_resolve", keys)
+    image, const = None, (0, 0, 0)
+    if torch.is_tensor(background):
+        image = _need(background, torch.uint8, "render_resolve: background").contiguous()
+        if tuple(image.shape) != (V, H, W, 3):
+            raise HipError(f"render_resolve: background image [{V},{H},{W},3], got {tuple(image.shape)}")
+    else:
+        const = tuple(int(v) for v in background)
+        if len(const) != 3:
+            raise HipError("render_resolve: background (r, g, b)")
+    rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=keys.device)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=keys.device)
+    _check(lib().bf_render_resolve(_ptr(keys), c_int(V), c_int(H), c_int(W), _ptr(image), c_int(const[0]), c_int(const[1]),
+                                   c_int(const[2]), _ptr(rgb), _ptr(depth), _stream()), "bf_render_resolve")
+    return rgb, depth
+
+
+# ------------------------------------------------------------------------------------------
 # evaluation against ground truth (bf_eval.hip; f64 throughout, off the timed path)
 # ------------------------------------------------------------------------------------------
 def _f64_rows(t, tail, name):

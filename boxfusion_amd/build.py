@@ -32,6 +32,7 @@ SOURCES = {
     "bf_fseq.hip": EXACT,
     "bf_cloud.hip": EXACT,
     "bf_eval.hip": EXACT,
+    "bf_render.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 

@@ -28,7 +28,6 @@ import argparse
 import itertools
 import json
 import os
-import pickle
 import struct
 import sys
 
@@ -234,14 +233,8 @@ def score(pred_corners, gt_corners, thresholds=(0.25, 0.5)):
 def load_boxes_pkl(path):
     """the corners f64 [n,8,3] of `<seq>_boxes.pkl` (results.global_save_list: [[(class, corners
     [8,3], score), ...]])"""
-    with open(path, "rb") as fh:
-        data = pickle.load(fh)
-    if not (isinstance(data, list) and len(data) == 1 and isinstance(data[0], list)):
-        raise ValueError(f"{path}: not a box list of results.global_save_list")
-    boxes = [np.asarray(rec[1], np.float64) for rec in data[0]]
-    if any(b.shape != (8, 3) for b in boxes):
-        raise ValueError(f"{path}: a record without [8,3] corners")
-    return np.stack(boxes) if boxes else np.zeros((0, 8, 3))
+    from boxfusion_amd.results import load_global_boxes
+    return load_global_boxes(path)
 
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",

@@ -289,7 +289,7 @@ class Pipeline:
         self.detect, self.fusion, self.gap = detect, fusion, gap
 
     def run(self, frames, n_frames, per_frame=True, frames_per_call=64, viz=None, cloud=None,
-            cloud_frames="keyframes", viz_points=False):
+            cloud_frames="keyframes", viz_points=False, snapshots=None):
         """frames(ids) -> (rgb [b,H,W,3] u8 dev, depth [b,H,W] f32 dev, poses [b,4,4] host).
         A frames callable that takes a `need_rgb` keyword is called with need_rgb=False for the
         non-keyframes whose RGB nothing reads (their per-frame work uses depth and pose only) and
@@ -304,7 +304,11 @@ class Pipeline:
         per_frame and asks the frame source for the non-keyframes' RGB), enqueued on the current
         stream right after the work that produced them and before the input buffers are reused.
         viz_points: hand viz.frame the frame's xyzrgb (demo.py:193's /world/xyz; read back per
-        batch).  All three are off by default."""
+        batch).
+        snapshots: a render.SnapshotWriter -- where viz gets the global boxes (after each keyframe's
+        fusion step and after the last frame) it writes that frame's RGB with the boxes drawn over
+        it as a PNG, and at the end the overviews of `cloud` (host side, like viz).
+        All four are off by default."""
         if cloud_frames not in ("keyframes", "all"):
             raise ValueError("cloud_frames: 'keyframes' or 'all'")
         if cloud is not None and cloud_frames == "all" and not per_frame:
@@ -373,10 +377,19 @@ class Pipeline:
                     for f in range(i + 1, min(i + self.gap, n_frames)):
                         if f in nk_pose:
                             viz.frame(f, *nk_pose[f])
+                if snapshots is not None:
+                    snapshots.snapshot(i, poses[j], rgb[j], self.fusion.all_pred_box)
         last = n_frames - 1
         if last % self.gap != 0:
-            _, _, p = nk_frames([last])
+            if snapshots is None:
+                _, _, p = nk_frames([last])
+            else:                      # the last frame's picture needs its RGB
+                last_rgb, _, p = frames([last], need_rgb=True) if lazy_rgb else frames([last])
             self.fusion.finish(last, p[0], False)
             if viz is not None:        # demo.py:330: the boxes after the last frame's block too
                 viz.boxes(self.fusion.all_pred_box, last)
+            if snapshots is not None:
+                snapshots.snapshot(last, p[0], last_rgb[0], self.fusion.all_pred_box)
+        if snapshots is not None:
+            snapshots.finish(cloud, self.fusion.all_pred_box)
         return self.fusion

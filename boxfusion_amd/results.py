@@ -56,6 +56,19 @@ def global_save_list(all_pred_box, class_list, dataset):
     return [[(int(0), boxes[n], 1.0) for n in range(len(all_pred_box))]]
 
 
+def load_global_boxes(filename):
+    """the corners f64 [n,8,3] of a `<video_id>_boxes.pkl` (global_save_list's [[(class, corners
+    [8,3], score), ...]])"""
+    with open(filename, "rb") as fh:
+        data = pickle.load(fh)
+    if not (isinstance(data, list) and len(data) == 1 and isinstance(data[0], list)):
+        raise ValueError(f"{filename}: not a box list of results.global_save_list")
+    boxes = [np.asarray(rec[1], np.float64) for rec in data[0]]
+    if any(b.shape != (8, 3) for b in boxes):
+        raise ValueError(f"{filename}: a record without [8,3] corners")
+    return np.stack(boxes) if boxes else np.zeros((0, 8, 3))
+
+
 def framewise_save_list(per_frame_ins, class_list):
     """demo.py:383-386: every per-frame detection with its class index and CLIP feature"""
     idx = _class_index(class_list, per_frame_ins.categories)

@@ -7,7 +7,8 @@ color/*.jpg, depth/*.png, pose/*.txt tree.
 of `DecodedFrameStream` for the exported tree of the same scene, the colour frames through
 bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zlib on the host);
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
-the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud (no model needed).
+the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud and `... render
+scene.sens OUT_DIR [--boxes SEQ_boxes.pkl]` orbit and top-down PNG views of it (no model needed).
 
 Layout (little-endian, packed): uint32 version (4), uint64 n + n bytes sensor name, four row-major
 4x4 float32 matrices (colour intrinsics / extrinsics, depth intrinsics / extrinsics), int32 colour
@@ -293,8 +294,17 @@ def cloud(sens, voxel=0.02, start=0, stop=None, step=1, max_depth=10.0, capacity
     return sc
 
 
-def main(argv=None):
+def _cloud_arguments(p):
+    p.add_argument("--voxel", type=float, default=0.02, help="voxel edge in metres")
+    p.add_argument("--start", type=int, default=0)
+    p.add_argument("--stop", type=int, default=None)
+    p.add_argument("--step", type=int, default=1)
+    p.add_argument("--max-depth", type=float, default=10.0)
+
+
+def parser():
     import argparse
+    from boxfusion_amd.render import add_render_arguments
     p = argparse.ArgumentParser(prog="python -m boxfusion_amd.sens", description="ScanNet .sens containers")
     sub = p.add_subparsers(dest="cmd", required=True)
     pi = sub.add_parser("info", help="print the header fields")
@@ -308,19 +318,28 @@ def main(argv=None):
     pc = sub.add_parser("cloud", help="write the scene's coloured point cloud (a voxel map) as a PLY")
     pc.add_argument("sens")
     pc.add_argument("out")
-    pc.add_argument("--voxel", type=float, default=0.02, help="voxel edge in metres")
-    pc.add_argument("--start", type=int, default=0)
-    pc.add_argument("--stop", type=int, default=None)
-    pc.add_argument("--step", type=int, default=1)
-    pc.add_argument("--max-depth", type=float, default=10.0)
+    _cloud_arguments(pc)
+    pr = sub.add_parser("render", help="write orbit and top-down PNG views of the scene's point cloud (and boxes)")
+    pr.add_argument("sens")
+    pr.add_argument("out", help="the directory of overview_<k>.png and overview_top.png")
+    _cloud_arguments(pr)
+    add_render_arguments(pr)
+    return p
+
+
+def main(argv=None):
+    p = parser()
     a = p.parse_args(argv)
-    if a.cmd == "cloud":
+    if a.cmd in ("cloud", "render"):
         if not a.voxel > 0:
             p.error("--voxel must be positive")
         if a.step < 1:
             p.error("--step must be at least 1")
         if not a.max_depth > 0:
             p.error("--max-depth must be positive")
+    if a.cmd == "render":
+        from boxfusion_amd import render
+        render.check_render_arguments(p, a)
     with SensFile(a.sens) as s:
         if a.cmd == "info":
             info(s)
@@ -329,6 +348,11 @@ def main(argv=None):
             n = sc.save_ply(a.out)
             print(f"{n} points -> {a.out}")
             print(" ".join(f"{k}={v}" for k, v in sc.stats().items()))
+        elif a.cmd == "render":
+            sc = cloud(s, a.voxel, a.start, a.stop, a.step, a.max_depth)
+            paths = render.write_overviews(sc, render.load_boxes_argument(a.boxes), a.out, views=a.views, size=a.size,
+                                           radius=a.radius)
+            print(f"{sc.stats()['stored']} points -> {len(paths)} views in {a.out}")
         else:
             frames = export(s, a.out, a.start, a.stop, a.step)
             print(f"{len(frames)} frames -> {a.out}")

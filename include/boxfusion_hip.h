@@ -678,6 +678,44 @@ int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint8_t* rg
 int bf_cloud_extract(const void* table, long long capacity, int64_t* key, uint32_t* count,
                      uint32_t* sums, int* n_out, int* block_counts, void* stream);
 
+/* ---- headless renderer (the reference shows the scene and the boxes in the rerun viewer, demo.py:35-65;
+ * here a z-buffer on the device draws them) ----
+ *
+ * The target is keys uint64 [V,H,W], one image per view.  key = layer << 63 | bits(Z) << 32 | R << 24 |
+ * G << 16 | B << 8 | 0xFF: Z the camera-space depth (f32 > 0), layer 1 = scene, 0 = overlay (drawn over
+ * the scene, depth-sorted within itself); empty = all ones.  Every draw is an atomicMin, so the image is
+ * the same bits whatever order the primitives arrive in.  cams: world -> camera rows f32 [V,12] (R
+ * row-major, then t); fx fy cx cy, H, W: one pinhole for all views; 1 <= V <= 65535, H, W <= 16384,
+ * near_z > 0.  All f32 arithmetic is left to right, uncontracted, with IEEE division.
+ *
+ * Every key of the target to empty. */
+int bf_render_clear(void* keys, int V, int H, int W, void* stream);
+
+/* n points (xyz f32 [n,3], rgb u8 [n,3]) into every view: X = R00 x + R01 y + R02 z + tx (Y, Z alike); kept
+ * when X, Y, Z are finite and near_z < Z < far_z; u = fx X / Z + cx, v = fy Y / Z + cy; kept when
+ * -(radius+1) <= u <= W + radius (v with H); the square of pixels within radius (0..4) of (floor(u + 0.5),
+ * floor(v + 0.5)), clipped to the image, takes the point's key.  stats: NULL, or uint64 [2] added to:
+ * pixels offered (splat pixels inside the image), atomics issued (the stored key was not already <=). */
+int bf_render_points(const float* xyz, const uint8_t* rgb, long long n, const float* cams, int V, float fx,
+                     float fy, float cx, float cy, int H, int W, float near_z, float far_z, int radius,
+                     int layer, void* keys, void* stats, void* stream);
+
+/* The twelve edges of B boxes (corners f32 [B,8,3] in the v0..v7 order, colors u8 [B,3], mask NULL or u8
+ * [B]: 0 skips the box) into every view.  A box with a non-finite corner is skipped whole.  Per edge: both
+ * ends to the camera; nothing when both are behind near_z, else the end behind becomes a + t (b - a), t =
+ * (near_z - Za) / (Zb - Za), at Z = near_z; projected as above with w = 1 / Z; the screen segment clipped to
+ * [-0.5, W - 0.5] x [-0.5, H - 0.5] (Liang-Barsky, t0..t1); n = min(ceil(max(|du|, |dv|)), max(W, H)) over
+ * the clipped part; samples i = 0..n at t = t0 + (t1 - t0) (i / max(n, 1)) with u, v, w linear in t and Z =
+ * 1 / w, each splatted like a point with radius half_width (0..2). */
+int bf_render_edges(const float* corners, const uint8_t* colors, const uint8_t* mask, int B, const float* cams,
+                    int V, float fx, float fy, float cx, float cy, int H, int W, float near_z, int half_width,
+                    int layer, void* keys, void* stream);
+
+/* keys -> rgb u8 [V,H,W,3] and depth f32 [V,H,W] (the stored Z; 0 where empty).  An empty pixel takes
+ * bg_image's pixel (u8 [V,H,W,3]) when that is not NULL, else the constant (bg_r, bg_g, bg_b). */
+int bf_render_resolve(const void* keys, int V, int H, int W, const uint8_t* bg_image, int bg_r, int bg_g,
+                      int bg_b, uint8_t* rgb, float* depth, void* stream);
+
 /* ---- depth PNG decode (reference: cv2.imread(depth_path, cv2.IMREAD_UNCHANGED),
  * capture_stream.py:197 ScanNet / :405 CA-1M) ----
  * F PNG files, back to back in device memory: file f = files[offsets[f] .. offsets[f+1]) (offsets
