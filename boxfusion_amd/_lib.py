@@ -1247,6 +1247,157 @@ def cloud_extract(table):
 
 
 # ------------------------------------------------------------------------------------------
+# scene mesh (bf_tsdf.hip)
+# ------------------------------------------------------------------------------------------
+TSDF_VOX, TSDF_FIELDS = 512, 6          # voxels of a block; int32 fields per voxel: w, sum q, cw, sum r g b
+TSDF_MAX_WEIGHT = 1 << 20
+TSDF_STATS = ("observations", "skipped_pose", "out_of_range", "dropped_full", "saturated", "blocks")
+
+
+def tsdf_volume(capacity, device):
+    """(keys int64 [capacity] all empty, touched int64 [capacity], vox int32 [capacity,6,512], stats
+    int64 [8]) zeroed, for tsdf_touch / tsdf_update"""
+    capacity = int(capacity)
+    if capacity <= 0 or capacity & (capacity - 1) or capacity >= 1 << 31:
+        raise HipError("tsdf_volume: capacity must be a power of two below 2^31")
+    return (torch.full((capacity,), -1, dtype=torch.int64, device=device),
+            torch.zeros(capacity, dtype=torch.int64, device=device),
+            torch.zeros((capacity, TSDF_FIELDS, TSDF_VOX), dtype=torch.int32, device=device),
+            torch.zeros(8, dtype=torch.int64, device=device))
+
+
+def _tsdf_frames(name, depth, poses, rgb=None):
+    depth = _need(depth, torch.float32, f"{name}: depth").contiguous()
+    poses = _need(poses, torch.float32, f"{name}: poses").contiguous()
+    if depth.dim() != 3 or not 0 < depth.shape[0] <= 64 or tuple(poses.shape) != (depth.shape[0], 4, 4):
+        raise HipError(f"{name}: depth [B,H,W] and poses [B,4,4] of 1..64 frames; got {tuple(depth.shape)}, "
+                       f"{tuple(poses.shape)}")
+    if rgb is not None:
+        rgb = _need(rgb, torch.uint8, f"{name}: rgb").contiguous()
+        if tuple(rgb.shape) != (*depth.shape, 3):
+            raise HipError(f"{name}: rgb [B,H,W,3] at the depth size, got {tuple(rgb.shape)}")
+    return depth, poses, rgb
+
+
+def _tsdf_arrays(name, keys, touched, vox=None, stats=None):
+    _need(keys, torch.int64, f"{name}: keys")
+    _need(touched, torch.int64, f"{name}: touched")
+    cap = keys.shape[0]
+    if keys.dim() != 1 or tuple(touched.shape) != (cap,):
+        raise HipError(f"{name}: keys / touched [capacity] of tsdf_volume")
+    if vox is not None and (vox.dtype != torch.int32 or tuple(vox.shape) != (cap, TSDF_FIELDS, TSDF_VOX)):
+        raise HipError(f"{name}: vox int32 [capacity,6,512] of tsdf_volume")
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 8):
+        raise HipError(f"{name}: stats int64 [8] of tsdf_volume")
+    return cap
+
+
+def _intr4(intr):
+    return [c_float(float(np.float32(v))) for v in intr]
+
+
+def _tsdf_touch_work(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, stats):
+    n = float(depth.numel())
+    return dict(kind="tsdf_touch", n=int(n)), 0.0, n * 4
+
+
+@_timed(_tsdf_touch_work)
+def tsdf_touch(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, stats):
+    """claim and mark the blocks within the truncation band of depth f32 [B,H,W] seen from poses f32
+    [B,4,4] (B <= 64) with the pinhole intr = (fx, fy, cx, cy) (bf_tsdf_touch)"""
+    depth, poses, _ = _tsdf_frames("tsdf_touch", depth, poses)
+    cap = _tsdf_arrays("tsdf_touch", keys, touched, stats=stats)
+    B, H, W = depth.shape
+    _check(lib().bf_tsdf_touch(_ptr(depth), _ptr(poses), c_int(B), c_int(H), c_int(W), *_intr4(intr),
+                               c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(max_depth)), _ptr(keys),
+                               _ptr(touched), ctypes.c_longlong(cap), _ptr(stats), _stream()), "bf_tsdf_touch")
+
+
+def _tsdf_update_work(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, vox, stats, rgb=None,
+                      max_weight=TSDF_MAX_WEIGHT):
+    return dict(kind="tsdf_update", n=int(depth.numel()), colour=rgb is not None), 0.0, float(depth.numel()) * 4
+
+
+@_timed(_tsdf_update_work)
+def tsdf_update(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, vox, stats, rgb=None,
+                max_weight=TSDF_MAX_WEIGHT):
+    """the frames of the tsdf_touch call before it into the voxels of the blocks it marked, and the
+    marks cleared (bf_tsdf_update); rgb u8 [B,H,W,3] at the depth size, or None for no colour"""
+    depth, poses, rgb = _tsdf_frames("tsdf_update", depth, poses, rgb)
+    cap = _tsdf_arrays("tsdf_update", keys, touched, vox, stats)
+    if not 1 <= int(max_weight) <= TSDF_MAX_WEIGHT:
+        raise HipError(f"tsdf_update: max_weight in 1..{TSDF_MAX_WEIGHT}")
+    B, H, W = depth.shape
+    dev = depth.device
+    slots = torch.empty(cap, dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
+    _check(lib().bf_tsdf_update(_ptr(depth), _ptr(rgb), _ptr(poses), c_int(B), c_int(H), c_int(W), *_intr4(intr),
+                                c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(max_depth)),
+                                c_int(int(max_weight)), _ptr(keys), _ptr(touched), _ptr(vox), ctypes.c_longlong(cap),
+                                _ptr(slots), _ptr(n), _ptr(work), _ptr(stats), _stream()), "bf_tsdf_update")
+
+
+def _tsdf_extract_work(keys):
+    return dict(kind="tsdf_extract", capacity=int(keys.shape[0])), 0.0, 20.0 * keys.shape[0]
+
+
+@_timed(_tsdf_extract_work)
+def tsdf_extract(keys):
+    """the occupied slots of a volume in slot order (bf_tsdf_extract): (key int64 [cap], slot int32
+    [cap], n int32 [1] on the device); rows past n are not written"""
+    _need(keys, torch.int64, "tsdf_extract: keys")
+    cap, dev = keys.shape[0], keys.device
+    key = torch.empty(cap, dtype=torch.int64, device=dev)
+    slot = torch.empty(cap, dtype=torch.int32, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
+    _check(lib().bf_tsdf_extract(_ptr(keys), ctypes.c_longlong(cap), _ptr(key), _ptr(slot), _ptr(n), _ptr(work),
+                                 _stream()), "bf_tsdf_extract")
+    return key, slot, n
+
+
+def _tsdf_surface_work(keys, vox, skey, sslot, voxel):
+    return dict(kind="tsdf_surface", blocks=int(skey.shape[0])), 0.0, float(skey.shape[0]) * TSDF_VOX * TSDF_FIELDS * 4
+
+
+@_timed(_tsdf_surface_work)
+def tsdf_surface(keys, vox, skey, sslot, voxel):
+    """naive surface nets over the occupied blocks sorted by key (skey int64 [n], sslot int32 [n]):
+    (vertices f32 [nv,3], rgb u8 [nv,3], faces int32 [nf,3]) (bf_tsdf_surface_count, one read-back of
+    the two totals, bf_tsdf_surface_write)"""
+    _need(keys, torch.int64, "tsdf_surface: keys")
+    _need(vox, torch.int32, "tsdf_surface: vox")
+    skey = _need(skey, torch.int64, "tsdf_surface: skey").contiguous()
+    sslot = _need(sslot, torch.int32, "tsdf_surface: sslot").contiguous()
+    cap, dev, n = keys.shape[0], keys.device, int(skey.shape[0])
+    if tuple(vox.shape) != (cap, TSDF_FIELDS, TSDF_VOX) or tuple(sslot.shape) != (n,) or n > cap:
+        raise HipError("tsdf_surface: keys [capacity], vox [capacity,6,512], skey / sslot [n <= capacity]")
+    empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.uint8, device=dev),
+             torch.empty((0, 3), dtype=torch.int32, device=dev))
+    if n == 0:
+        return empty
+    rank = torch.empty(cap, dtype=torch.int32, device=dev)
+    bitmap = torch.empty((n, 8), dtype=torch.int64, device=dev)
+    eflags = torch.empty((n, TSDF_VOX), dtype=torch.uint8, device=dev)
+    vprefix = torch.empty(n, dtype=torch.int32, device=dev)
+    fprefix = torch.empty(n, dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    head = (_ptr(keys), ctypes.c_longlong(cap), _ptr(vox), _ptr(skey), _ptr(sslot), c_int(n), _ptr(rank), _ptr(bitmap),
+            _ptr(eflags), _ptr(vprefix), _ptr(fprefix))
+    _check(lib().bf_tsdf_surface_count(*head, _ptr(totals), _stream()), "bf_tsdf_surface_count")
+    nv, nq = totals.cpu().tolist()
+    if nv == 0:
+        return empty
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    vrgb = torch.empty((nv, 3), dtype=torch.uint8, device=dev)
+    faces = torch.empty((max(2 * nq, 1), 3), dtype=torch.int32, device=dev)
+    _check(lib().bf_tsdf_surface_write(*head, c_float(float(voxel)), _ptr(verts), _ptr(vrgb), _ptr(faces), _stream()),
+           "bf_tsdf_surface_write")
+    return verts, vrgb, faces[:2 * nq]
+
+
+# ------------------------------------------------------------------------------------------
 # headless renderer (bf_render.hip)
 # ------------------------------------------------------------------------------------------
 def _render_target(name, keys):

@@ -11,10 +11,8 @@
 //   bf_cloud_extract      the occupied slots, compacted (in slot order)
 // Voxel slot (5 x u64; low u32, high u32): key; count, sum_qx; sum_qy, sum_qz; sum_r, sum_g; sum_b, 0.
 // A field holds at most 255 * 2^24 < 2^32, so the packed 64-bit adds never carry from the low field into the high.
-#include "bf_common.h"
+#include "bf_compact.h"
 
-#define CLOUD_BLOCK 256
-#define CLOUD_WAVES (CLOUD_BLOCK / 64)
 #define CLOUD_SLOT_WORDS 5
 #define CLOUD_EMPTY 0xFFFFFFFFFFFFFFFFull
 #define CLOUD_MAX_COUNT (1u << 24)
@@ -107,61 +105,6 @@ BF_API int bf_resize_bicubic_u8(const uint8_t* src, int F, int Hs, int Ws, int H
 }
 
 // ---- stable compaction: block counts, their scan, the scatter ---------------------------------------------------
-// position of this thread's item among the block's selected items, and the block's total (in every thread)
-__device__ __forceinline__ int block_rank(bool sel, int& block_total) {
-    __shared__ int wave_n[CLOUD_WAVES];
-    const unsigned long long m = __ballot(sel);
-    const int w = threadIdx.x >> 6;
-    if (bf_lane() == 0) wave_n[w] = __popcll(m);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < CLOUD_WAVES; ++i) {
-        const int n = wave_n[i];
-        base += i < w ? n : 0;
-        tot += n;
-    }
-    block_total = tot;
-    return base + bf_lanes_below(m);
-}
-
-// counts [nb] -> exclusive prefix in place; marks[i] = prefix[i * stride] for i < n_marks, marks[n_marks] = total.
-// One block of 1024 threads; each thread owns a contiguous chunk of the counts.
-__global__ void __launch_bounds__(1024) k_scan_counts(int* __restrict__ counts, int nb, int stride, int* __restrict__ marks,
-                                                      int n_marks) {
-    __shared__ int wave_sum[16];
-    const int t = threadIdx.x;
-    const int chunk = (nb + 1023) / 1024;
-    const int lo = t * chunk < nb ? t * chunk : nb;
-    const int hi = lo + chunk < nb ? lo + chunk : nb;
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += counts[i];
-    // inclusive scan of s over the wave, then over the 16 waves
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(inc, o, 64);
-        if (bf_lane() >= o) inc += v;
-    }
-    if (bf_lane() == 63) wave_sum[t >> 6] = inc;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int n = wave_sum[i];
-        base += i < (t >> 6) ? n : 0;
-        total += n;
-    }
-    int run = base + inc - s;
-    for (int i = lo; i < hi; ++i) {
-        const int c = counts[i];
-        counts[i] = run;
-        if (stride > 0 && i % stride == 0 && i / stride < n_marks) marks[i / stride] = run;
-        run += c;
-    }
-    if (t == 0) marks[n_marks] = total;
-}
-
 __global__ void __launch_bounds__(CLOUD_BLOCK) k_pack_count(const uint8_t* __restrict__ valid, int hw, int bpf,
                                                             int* __restrict__ counts) {
     const int f = blockIdx.x / bpf, j = blockIdx.x - f * bpf;
@@ -216,15 +159,6 @@ BF_API int bf_cloud_pack(const float* xyz, const uint8_t* valid, const uint8_t* 
 
 // ---- voxel hash map -----------------------------------------------------------------------------------------------
 enum { ST_STORED = 0, ST_NONFINITE, ST_OUT_OF_RANGE, ST_DROPPED_FULL, ST_SATURATED, ST_RUNS, ST_N = 8 };
-
-__device__ __forceinline__ unsigned long long cloud_hash(unsigned long long k) {
-    k ^= k >> 30;
-    k *= 0xBF58476D1CE4E5B9ull;
-    k ^= k >> 27;
-    k *= 0x94D049BB133111EBull;
-    k ^= k >> 31;
-    return k;
-}
 
 // the slot of `key` (claimed if new), or -1 when neither the key nor an empty slot was found in `cap` probes.
 // Slots never empty again, so a stale read can only show EMPTY where a key now sits, and the compare-and-swap

@@ -1,0 +1,550 @@
+// bf_tsdf.hip — the scene mesh: a sparse truncated-signed-distance volume fused from posed depth frames, and a
+// naive-surface-nets extractor over it (the reference leaves mesh.ply to open3d, data_process/README.md:48):
+//   bf_tsdf_touch          the 8x8x8-voxel blocks within the truncation band of every valid depth pixel, claimed in
+//                          an open-addressing hash map (cloud_find's design) and marked with the frame's bit
+//   bf_tsdf_update         the touched blocks compacted (count / scan / scatter), then one workgroup per block and
+//                          one thread per voxel: every frame whose bit is set is projected into and added
+//   bf_tsdf_extract        the occupied slots, compacted (in slot order)
+//   bf_tsdf_surface_count  over the key-sorted blocks: the cells that get a vertex, the grid edges that get a quad,
+//   bf_tsdf_surface_write  their scans, and the vertices / triangles written at the scanned positions
+// The volume is three arrays over `capacity` slots: keys u64 (three block indices biased by 2^20, 21 bits each;
+// all ones = empty), touched u64 (bit f = frame f of the launch in flight reaches this block) and vox
+// int32 [capacity, 6, 512]: per voxel (x fastest, then y, then z)
+//   field 0  w      observations          <= max_weight <= 2^20
+//   field 1  sum q  q = rint(min(sdf / trunc, 1) * 1024) in [-1024, 1024], |sum| <= 2^30
+//   field 2  cw     coloured observations <= w
+//   field 3-5  sum r, g, b                <= 255 * 2^20 < 2^28
+// Integers only: adds commute, so the volume after a set of frames is the same bits whatever the frame order or
+// batching, as long as no voxel reached max_weight (such a voxel refuses the observation, counted in `saturated`).
+#include "bf_compact.h"
+
+#define TSDF_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define TSDF_VOX 512
+#define TSDF_FIELDS 6
+#define TSDF_BLOCK_WORDS (TSDF_VOX * TSDF_FIELDS)
+#define TSDF_BIAS (1 << 20)
+#define TSDF_KEY_MASK 0x1FFFFFull
+#define TSDF_MAX_WEIGHT (1 << 20)
+#define TSDF_UPDATE_GRID 2048
+
+enum { TS_OBSERVATIONS = 0, TS_SKIPPED_POSE, TS_OUT_OF_RANGE, TS_DROPPED_FULL, TS_SATURATED, TS_BLOCKS, TS_N = 8 };
+
+typedef unsigned long long u64;
+
+// the slot of `key` (claimed if new, then *claimed is set), or -1 when neither the key nor an empty slot was
+// found in capacity probes; slots never empty again and nothing here waits for another lane or wave
+__device__ __forceinline__ long long tsdf_find(u64* keys, u64 mask, u64 key, bool* claimed) {
+    u64 s = cloud_hash(key) & mask;
+    for (u64 i = 0; i <= mask; ++i, s = (s + 1) & mask) {
+        u64 k = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == TSDF_EMPTY) {
+            k = atomicCAS(keys + s, TSDF_EMPTY, key);
+            if (k == TSDF_EMPTY) {
+                *claimed = true;
+                return (long long)s;
+            }
+        }
+        if (k == key) return (long long)s;
+    }
+    return -1;
+}
+
+// the slot of `key` in a table nobody is writing, or -1
+__device__ __forceinline__ int tsdf_lookup(const u64* __restrict__ keys, u64 mask, u64 key) {
+    u64 s = cloud_hash(key) & mask;
+    for (u64 i = 0; i <= mask; ++i, s = (s + 1) & mask) {
+        const u64 k = keys[s];
+        if (k == key) return (int)s;
+        if (k == TSDF_EMPTY) return -1;
+    }
+    return -1;
+}
+
+__device__ __forceinline__ void tsdf_stat(unsigned* block_stats, int which, bool flag) {
+    const u64 m = __ballot(flag);
+    if (m && bf_lane() == 0) atomicAdd(block_stats + which, (unsigned)__popcll(m));
+}
+
+// ---- touch: one thread per depth pixel, blockIdx.x = frame * bpf + the frame's block -------------------------------
+__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_touch(const float* __restrict__ depth, const float* __restrict__ poses,
+                                                            int hw, int W, int bpf, float fx, float fy, float cx, float cy,
+                                                            float voxel, int T, float max_depth, u64* __restrict__ keys,
+                                                            u64* __restrict__ touched, u64 mask, u64* __restrict__ stats) {
+    __shared__ unsigned bstats[TS_N];
+    const int f = blockIdx.x / bpf, j = blockIdx.x - f * bpf;
+    const float* P = poses + 16 * f;
+    bool finite = true;
+    for (int i = 0; i < 16; ++i) finite = finite && isfinite(P[i]);
+    if (!finite) {                                               // the whole frame, so the whole block: lost tracking
+        if (j == 0 && threadIdx.x == 0) atomicAdd(stats + TS_SKIPPED_POSE, 1ull);
+        return;
+    }
+    if (threadIdx.x < TS_N) bstats[threadIdx.x] = 0;
+    __syncthreads();
+    const int p = j * CLOUD_BLOCK + threadIdx.x;
+    const int lane = bf_lane();
+    float d = p < hw ? depth[(size_t)f * hw + p] : 0.f;
+    const bool live = d > 0.f && d < max_depth;                  // NaN fails
+    const float xu = (float)(p % W) - cx, yv = (float)(p / W) - cy;
+    const float bs = 8.0f * voxel;
+    const float lim = 1048576.0f;                                // 2^20 blocks
+    const u64 bit = 1ull << f;
+    u64 prev_key = TSDF_EMPTY;                                   // the key this thread handled last
+    for (int k = -T; k <= T; ++k) {
+        u64 key = TSDF_EMPTY;
+        bool out_of_range = false;
+        if (live) {
+            const float z = d + (float)k * voxel;
+            const float xc = xu * z / fx, yc = yv * z / fy;
+            const float bx = floorf((P[0] * xc + P[1] * yc + P[2] * z + P[3]) / bs);
+            const float by = floorf((P[4] * xc + P[5] * yc + P[6] * z + P[7]) / bs);
+            const float bz = floorf((P[8] * xc + P[9] * yc + P[10] * z + P[11]) / bs);
+            if (bx >= -lim && bx < lim && by >= -lim && by < lim && bz >= -lim && bz < lim)
+                key = ((u64)((int)bx + TSDF_BIAS) << 42) | ((u64)((int)by + TSDF_BIAS) << 21) | (u64)((int)bz + TSDF_BIAS);
+            else
+                out_of_range = true;
+        }
+        tsdf_stat(bstats, TS_OUT_OF_RANGE, out_of_range);
+        // equal keys merge over this thread's adjacent samples and over adjacent lanes: one probe per run
+        const u64 want = key != prev_key ? key : TSDF_EMPTY;
+        const u64 left = __shfl_up(want, 1, 64);
+        const bool head = want != TSDF_EMPTY && (lane == 0 || left != want);
+        bool claimed = false, dropped = false;
+        if (head) {
+            const long long slot = tsdf_find(keys, mask, want, &claimed);
+            if (slot >= 0)
+                atomicOr(touched + slot, bit);
+            else
+                dropped = true;
+        }
+        tsdf_stat(bstats, TS_BLOCKS, claimed);
+        tsdf_stat(bstats, TS_DROPPED_FULL, dropped);
+        if (key != TSDF_EMPTY) prev_key = key;
+    }
+    __syncthreads();
+    if (threadIdx.x < TS_N && bstats[threadIdx.x]) atomicAdd(stats + threadIdx.x, (u64)bstats[threadIdx.x]);
+}
+
+BF_API int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, int W, float fx, float fy, float cx,
+                         float cy, float voxel, int trunc_voxels, float max_depth, void* keys, void* touched,
+                         long long capacity, void* stats, void* stream) {
+    if (!depth || !poses || !keys || !touched || !stats || B <= 0 || B > 64 || H <= 0 || W <= 0 || capacity <= 0 ||
+        (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 || trunc_voxels > 64 || !(max_depth > 0.f) ||
+        !(fx > 0.f) || !(fy > 0.f))
+        return BF_ERR_ARG;
+    const long long hw = (long long)H * W;
+    const long long bpf = (hw + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
+    if (capacity >= (1ll << 31) || hw * B >= (1ll << 31) || bpf * B >= (1ll << 31)) return BF_ERR_CAPACITY;
+    hipLaunchKernelGGL(k_tsdf_touch, dim3((unsigned)(bpf * B)), dim3(CLOUD_BLOCK), 0, bf_stream(stream), depth, poses,
+                       (int)hw, W, (int)bpf, fx, fy, cx, cy, voxel, trunc_voxels, max_depth, (u64*)keys, (u64*)touched,
+                       (u64)(capacity - 1), (u64*)stats);
+    return bf_check_launch();
+}
+
+// ---- compaction of the slots with a non-zero word (the touched blocks) or a key (the occupied blocks) ------------------
+// key_out == nullptr: select by words[s] != 0; else by words[s] != EMPTY and write the key beside the slot
+__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_slot_count(const u64* __restrict__ words, long long cap, u64 none,
+                                                                 int* __restrict__ counts) {
+    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
+    const bool sel = s < cap && words[s] != none;
+    int tot;
+    block_rank(sel, tot);
+    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_slot_scatter(const u64* __restrict__ words, long long cap, u64 none,
+                                                                   const int* __restrict__ prefix, int* __restrict__ slot_out,
+                                                                   long long* __restrict__ key_out) {
+    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
+    const bool sel = s < cap && words[s] != none;
+    int tot;
+    const int r = block_rank(sel, tot);
+    if (!sel) return;
+    const size_t o = (size_t)prefix[blockIdx.x] + r;
+    slot_out[o] = (int)s;
+    if (key_out) key_out[o] = (long long)words[s];
+}
+
+static void tsdf_compact(const u64* words, long long cap, u64 none, int* slot_out, long long* key_out, int* n_out,
+                         int* block_counts, hipStream_t st) {
+    const unsigned nb = (unsigned)((cap + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
+    hipLaunchKernelGGL(k_tsdf_slot_count, dim3(nb), dim3(CLOUD_BLOCK), 0, st, words, cap, none, block_counts);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, block_counts, (int)nb, 0, n_out, 0);
+    hipLaunchKernelGGL(k_tsdf_slot_scatter, dim3(nb), dim3(CLOUD_BLOCK), 0, st, words, cap, none,
+                       (const int*)block_counts, slot_out, key_out);
+}
+
+// ---- update: a workgroup per touched block, a thread per voxel -----------------------------------------------------------
+__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_update(const float* __restrict__ depth, const uint8_t* __restrict__ rgb,
+                                                          const float* __restrict__ poses, int B, int H, int W, float fx, float fy,
+                                                          float cx, float cy, float voxel, int T, float max_depth,
+                                                          int max_weight, const u64* __restrict__ keys, u64* __restrict__ touched,
+                                                          int* __restrict__ vox, const int* __restrict__ list,
+                                                          const int* __restrict__ n_list, u64* __restrict__ stats) {
+    __shared__ unsigned bstats[TS_N];
+    if (threadIdx.x < TS_N) bstats[threadIdx.x] = 0;
+    __syncthreads();
+    const int t = threadIdx.x;
+    const int n = *n_list;
+    const float trunc = (float)T * voxel;
+    const size_t hw = (size_t)H * W;
+    unsigned n_obs = 0, n_sat = 0;
+    for (int b = blockIdx.x; b < n; b += gridDim.x) {
+        const int slot = list[b];
+        const u64 key = keys[slot];
+        u64 word = touched[slot] & (B < 64 ? (1ull << B) - 1ull : ~0ull);     // the frames of this launch only
+        const int ix = ((int)((key >> 42) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + (t & 7);
+        const int iy = ((int)((key >> 21) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + ((t >> 3) & 7);
+        const int iz = ((int)(key & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + (t >> 6);
+        const float px = ((float)ix + 0.5f) * voxel, py = ((float)iy + 0.5f) * voxel, pz = ((float)iz + 0.5f) * voxel;
+        int* vb = vox + (size_t)slot * TSDF_BLOCK_WORDS + t;
+        int w = vb[0], sq = vb[TSDF_VOX], cw = vb[2 * TSDF_VOX], sr = vb[3 * TSDF_VOX], sg = vb[4 * TSDF_VOX],
+            sb = vb[5 * TSDF_VOX];
+        while (word) {
+            const int f = __ffsll((long long)word) - 1;          // the same in every thread of the workgroup
+            word &= word - 1;
+            const float* P = poses + 16 * f;
+            const float dx = px - P[3], dy = py - P[7], dz = pz - P[11];
+            const float z = P[2] * dx + P[6] * dy + P[10] * dz;
+            if (!(z > 0.f)) continue;
+            const float x = P[0] * dx + P[4] * dy + P[8] * dz, y = P[1] * dx + P[5] * dy + P[9] * dz;
+            const float fu = floorf(fx * x / z + cx + 0.5f), fv = floorf(fy * y / z + cy + 0.5f);
+            if (!(fu >= 0.f && fu < (float)W && fv >= 0.f && fv < (float)H)) continue;
+            const size_t pix = (size_t)f * hw + (size_t)(int)fv * W + (int)fu;
+            const float d = depth[pix];
+            if (!(d > 0.f && d < max_depth)) continue;
+            const float sdf = d - z;
+            if (sdf < -trunc) continue;
+            if (w >= max_weight) {
+                ++n_sat;
+                continue;
+            }
+            sq += (int)rintf(fminf(sdf / trunc, 1.0f) * 1024.0f);
+            w += 1;
+            ++n_obs;
+            if (rgb && sdf <= trunc) {
+                const uint8_t* c = rgb + pix * 3;
+                sr += c[0];
+                sg += c[1];
+                sb += c[2];
+                cw += 1;
+            }
+        }
+        vb[0] = w;
+        vb[TSDF_VOX] = sq;
+        vb[2 * TSDF_VOX] = cw;
+        vb[3 * TSDF_VOX] = sr;
+        vb[4 * TSDF_VOX] = sg;
+        vb[5 * TSDF_VOX] = sb;
+        __syncthreads();                                         // every thread has read the word
+        if (t == 0) touched[slot] = 0;
+    }
+    n_obs = (unsigned)bf_wave_sum_i32((int)n_obs);
+    n_sat = (unsigned)bf_wave_sum_i32((int)n_sat);
+    if (bf_lane() == 0) {
+        if (n_obs) atomicAdd(bstats + TS_OBSERVATIONS, n_obs);
+        if (n_sat) atomicAdd(bstats + TS_SATURATED, n_sat);
+    }
+    __syncthreads();
+    if (threadIdx.x < TS_N && bstats[threadIdx.x]) atomicAdd(stats + threadIdx.x, (u64)bstats[threadIdx.x]);
+}
+
+BF_API int bf_tsdf_update(const float* depth, const uint8_t* rgb, const float* poses, int B, int H, int W, float fx,
+                          float fy, float cx, float cy, float voxel, int trunc_voxels, float max_depth, int max_weight,
+                          const void* keys, void* touched, int32_t* vox, long long capacity, int* list, int* n_list,
+                          int* block_counts, void* stats, void* stream) {
+    if (!depth || !poses || !keys || !touched || !vox || !list || !n_list || !block_counts || !stats || B <= 0 || B > 64 ||
+        H <= 0 || W <= 0 || capacity <= 0 || (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 ||
+        trunc_voxels > 64 || !(max_depth > 0.f) || max_weight < 1 || max_weight > TSDF_MAX_WEIGHT || !(fx > 0.f) ||
+        !(fy > 0.f))
+        return BF_ERR_ARG;
+    if (capacity >= (1ll << 31) || (long long)H * W * B >= (1ll << 31)) return BF_ERR_CAPACITY;
+    hipStream_t st = bf_stream(stream);
+    tsdf_compact((const u64*)touched, capacity, 0ull, list, nullptr, n_list, block_counts, st);
+    // the list's length is on the device: enough workgroups to fill the machine twice over stride over it
+    const unsigned grid = (unsigned)(capacity < TSDF_UPDATE_GRID ? capacity : TSDF_UPDATE_GRID);
+    hipLaunchKernelGGL(k_tsdf_update, dim3(grid), dim3(TSDF_VOX), 0, st, depth, rgb, poses, B, H, W, fx, fy, cx, cy, voxel,
+                       trunc_voxels, max_depth, max_weight, (const u64*)keys, (u64*)touched, (int*)vox, (const int*)list,
+                       (const int*)n_list, (u64*)stats);
+    return bf_check_launch();
+}
+
+BF_API int bf_tsdf_extract(const void* keys, long long capacity, int64_t* key, int* slot, int* n_out, int* block_counts,
+                           void* stream) {
+    if (!keys || !key || !slot || !n_out || !block_counts || capacity <= 0) return BF_ERR_ARG;
+    if (capacity >= (1ll << 31)) return BF_ERR_CAPACITY;
+    tsdf_compact((const u64*)keys, capacity, TSDF_EMPTY, slot, (long long*)key, n_out, block_counts, bf_stream(stream));
+    return bf_check_launch();
+}
+
+// ---- naive surface nets over the key-sorted blocks -------------------------------------------------------------------------
+// A block's cells are the 8^3 cubes whose minimum corner is one of its voxel centres; their corners are the
+// block's own samples and the low faces of the seven blocks towards +x / +y / +z.
+// bit 25 of a staged sample's word: w > 0; bit 24: cw > 0; bits 0-23: the rounded mean colour
+#define SURF_EDGE 9
+#define SURF_SAMPLES (SURF_EDGE * SURF_EDGE * SURF_EDGE)
+
+// key of the block at (dx, dy, dz) from `key`, or EMPTY past the index range
+__device__ __forceinline__ u64 tsdf_neighbour_key(u64 key, int dx, int dy, int dz) {
+    const long long x = (long long)((key >> 42) & TSDF_KEY_MASK) + dx, y = (long long)((key >> 21) & TSDF_KEY_MASK) + dy,
+                    z = (long long)(key & TSDF_KEY_MASK) + dz;
+    const long long top = (long long)TSDF_KEY_MASK;
+    if (x < 0 || x > top || y < 0 || y > top || z < 0 || z > top) return TSDF_EMPTY;
+    return ((u64)x << 42) | ((u64)y << 21) | (u64)z;
+}
+
+// WRITE = false: bitmap [n,8] (bit c of word z: cell (c & 7, c >> 3, z) gets a vertex), eflags [n,512] (bits 0-2:
+// the cell's edge from its minimum corner along x / y / z changes sign; bit 3: that corner is inside), vcount [n],
+// rank_of_slot.  WRITE = true: the vertices at vcount (now the exclusive prefix) + the cell's rank.
+template <bool WRITE>
+__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__ keys, u64 mask, const int* __restrict__ vox,
+                                                         const long long* __restrict__ skey, const int* __restrict__ sslot,
+                                                         int* __restrict__ rank_of_slot, u64* __restrict__ bitmap,
+                                                         uint8_t* __restrict__ eflags, int* __restrict__ vcount, float voxel,
+                                                         float* __restrict__ verts, uint8_t* __restrict__ vrgb) {
+    __shared__ float s_val[SURF_SAMPLES];
+    __shared__ unsigned s_tag[SURF_SAMPLES];
+    __shared__ int nslot[8];
+    __shared__ int wave_n[8];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const u64 key = (u64)skey[b];
+    if (t < 8) {
+        int s = sslot[b];
+        if (t) {
+            const u64 nk = tsdf_neighbour_key(key, t & 1, (t >> 1) & 1, t >> 2);
+            s = nk == TSDF_EMPTY ? -1 : tsdf_lookup(keys, mask, nk);
+        }
+        nslot[t] = s;
+    }
+    __syncthreads();
+    for (int j = t; j < SURF_SAMPLES; j += TSDF_VOX) {
+        const int x = j % SURF_EDGE, y = (j / SURF_EDGE) % SURF_EDGE, z = j / (SURF_EDGE * SURF_EDGE);
+        const int s = nslot[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
+        float val = 0.f;
+        unsigned tag = 0;
+        if (s >= 0) {
+            const int* v = vox + (size_t)s * TSDF_BLOCK_WORDS + ((x & 7) | ((y & 7) << 3) | ((z & 7) << 6));
+            const int w = v[0];
+            if (w > 0) {
+                val = (float)v[TSDF_VOX] / (float)w;
+                tag = 1u << 25;
+                const int cw = v[2 * TSDF_VOX];
+                if (cw > 0) {
+                    const unsigned h = (unsigned)cw >> 1, c = (unsigned)cw;
+                    tag |= (1u << 24) | (((unsigned)v[3 * TSDF_VOX] + h) / c) | ((((unsigned)v[4 * TSDF_VOX] + h) / c) << 8) |
+                           ((((unsigned)v[5 * TSDF_VOX] + h) / c) << 16);
+                }
+            }
+        }
+        s_val[j] = val;
+        s_tag[j] = tag;
+    }
+    __syncthreads();
+    const int x = t & 7, y = (t >> 3) & 7, z = t >> 6;
+    const int base = x + SURF_EDGE * y + SURF_EDGE * SURF_EDGE * z;
+    float sv[8];
+    unsigned tg[8];
+    bool valid = true;
+    int n_in = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int j = base + (c & 1) + SURF_EDGE * ((c >> 1) & 1) + SURF_EDGE * SURF_EDGE * (c >> 2);
+        sv[c] = s_val[j];
+        tg[c] = s_tag[j];
+        valid = valid && (tg[c] >> 25);
+        n_in += sv[c] < 0.f;
+    }
+    const bool active = valid && n_in > 0 && n_in < 8;
+    const u64 m = __ballot(active);
+    if (bf_lane() == 0) wave_n[z] = __popcll(m);
+    __syncthreads();
+    if (!WRITE) {
+        if (bf_lane() == 0) bitmap[(size_t)b * 8 + z] = m;
+        unsigned fl = 0;
+        if (active)
+            fl = (unsigned)((sv[0] < 0.f) != (sv[1] < 0.f)) | ((unsigned)((sv[0] < 0.f) != (sv[2] < 0.f)) << 1) |
+                 ((unsigned)((sv[0] < 0.f) != (sv[4] < 0.f)) << 2) | ((unsigned)(sv[0] < 0.f) << 3);
+        eflags[(size_t)b * TSDF_VOX + t] = (uint8_t)fl;
+        if (t == 0) {
+            int tot = 0;
+            for (int i = 0; i < 8; ++i) tot += wave_n[i];
+            vcount[b] = tot;
+            rank_of_slot[sslot[b]] = b;
+        }
+        return;
+    }
+    if (!active) return;
+    int rank = vcount[b] + bf_lanes_below(m);
+    for (int i = 0; i < z; ++i) rank += wave_n[i];
+    // the mean of the crossings of the sign-changing edges: four x-edges, four y-edges, four z-edges
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    int ne = 0;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        const int ax = e >> 2, i = e & 3;
+        const int ca = ax == 0 ? 2 * i : (ax == 1 ? (i & 1) + 4 * (i >> 1) : i);
+        const int cb = ca + (1 << ax);
+        const float a = sv[ca], bb = sv[cb];
+        if ((a < 0.f) != (bb < 0.f)) {
+            const float tt = a / (a - bb);
+            sx += ax == 0 ? tt : (float)(ca & 1);
+            sy += ax == 1 ? tt : (float)((ca >> 1) & 1);
+            sz += ax == 2 ? tt : (float)(ca >> 2);
+            ++ne;
+        }
+    }
+    const float cnt = (float)ne;
+    const int ix = ((int)((key >> 42) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + x;
+    const int iy = ((int)((key >> 21) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + y;
+    const int iz = ((int)(key & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + z;
+    float* o = verts + (size_t)rank * 3;
+    o[0] = (((float)ix + 0.5f) + sx / cnt) * voxel;
+    o[1] = (((float)iy + 0.5f) + sy / cnt) * voxel;
+    o[2] = (((float)iz + 0.5f) + sz / cnt) * voxel;
+    unsigned r = 0, g = 0, bl = 0, nc = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+        if ((tg[c] >> 24) & 1u) {
+            r += tg[c] & 255u;
+            g += (tg[c] >> 8) & 255u;
+            bl += (tg[c] >> 16) & 255u;
+            ++nc;
+        }
+    uint8_t* oc = vrgb + (size_t)rank * 3;
+    oc[0] = (uint8_t)(nc ? (r + nc / 2) / nc : 128u);
+    oc[1] = (uint8_t)(nc ? (g + nc / 2) / nc : 128u);
+    oc[2] = (uint8_t)(nc ? (bl + nc / 2) / nc : 128u);
+}
+
+// the vertex of cell (x, y, z) of the block at sorted position r (coordinates in 0..7), or -1 if it has none
+__device__ __forceinline__ int tsdf_cell_vertex(const u64* __restrict__ bitmap, const int* __restrict__ vprefix, int r, int x,
+                                                int y, int z) {
+    const u64* bm = bitmap + (size_t)r * 8;
+    const int c = x + 8 * y;
+    const u64 word = bm[z];
+    if (!((word >> c) & 1ull)) return -1;
+    int v = vprefix[r] + __popcll(c ? word & ((1ull << c) - 1ull) : 0ull);
+    for (int i = 0; i < z; ++i) v += __popcll(bm[i]);
+    return v;
+}
+
+// a quad per sign-changing edge (from the cell's minimum corner along axis a) whose four cells have a vertex: the
+// cells at 0, -e_b, -e_b-e_c, -e_c with (a, b, c) cyclic run counter-clockwise seen from +a
+template <bool WRITE>
+__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_faces(const u64* __restrict__ keys, u64 mask, const long long* __restrict__ skey,
+                                                         const int* __restrict__ rank_of_slot, const u64* __restrict__ bitmap,
+                                                         const uint8_t* __restrict__ eflags, const int* __restrict__ vprefix,
+                                                         int* __restrict__ fcount, int* __restrict__ faces) {
+    __shared__ int nrank[8];
+    __shared__ int wave_n[8];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (t < 8) {
+        int r = b;
+        if (t) {
+            const u64 nk = tsdf_neighbour_key((u64)skey[b], -(t & 1), -((t >> 1) & 1), -(t >> 2));
+            const int s = nk == TSDF_EMPTY ? -1 : tsdf_lookup(keys, mask, nk);
+            r = s < 0 ? -1 : rank_of_slot[s];
+        }
+        nrank[t] = r;
+    }
+    __syncthreads();
+    const unsigned fl = eflags[(size_t)b * TSDF_VOX + t];
+    const int xyz[3] = {t & 7, (t >> 3) & 7, t >> 6};
+    int quad[3][4];
+    int nq = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        quad[a][0] = -1;
+        if (!((fl >> a) & 1u)) continue;
+        const int bx = (a + 1) % 3, cx = (a + 2) % 3;
+        bool all = true;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int c[3] = {xyz[0], xyz[1], xyz[2]};
+            c[bx] -= (k == 1 || k == 2);
+            c[cx] -= (k == 2 || k == 3);
+            const int r = nrank[(c[0] < 0) | ((c[1] < 0) << 1) | ((c[2] < 0) << 2)];
+            const int v = r < 0 ? -1 : tsdf_cell_vertex(bitmap, vprefix, r, c[0] & 7, c[1] & 7, c[2] & 7);
+            quad[a][k] = v;
+            all = all && v >= 0;
+        }
+        if (!all) quad[a][0] = -1;
+        nq += all;
+    }
+    // exclusive prefix of nq over the workgroup, in cell order
+    int inc = nq;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(inc, o, 64);
+        if (bf_lane() >= o) inc += v;
+    }
+    if (bf_lane() == 63) wave_n[t >> 6] = inc;
+    __syncthreads();
+    int at = inc - nq, tot = 0;
+    for (int i = 0; i < 8; ++i) {
+        at += i < (t >> 6) ? wave_n[i] : 0;
+        tot += wave_n[i];
+    }
+    if (!WRITE) {
+        if (t == 0) fcount[b] = tot;
+        return;
+    }
+    int* o = faces + ((size_t)fcount[b] + at) * 6;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (quad[a][0] < 0) continue;
+        const bool fwd = (fl >> 3) & 1u;                         // inside at the minimum corner: the normal is +a
+        const int v0 = quad[a][0], v1 = fwd ? quad[a][1] : quad[a][3], v2 = quad[a][2], v3 = fwd ? quad[a][3] : quad[a][1];
+        o[0] = v0;
+        o[1] = v1;
+        o[2] = v2;
+        o[3] = v0;
+        o[4] = v2;
+        o[5] = v3;
+        o += 6;
+    }
+}
+
+static bool tsdf_surface_args(const void* keys, long long capacity, const void* skey, const void* sslot, int n,
+                              const void* rank_of_slot, const void* bitmap, const void* eflags, const void* vprefix,
+                              const void* fprefix) {
+    return keys && skey && sslot && rank_of_slot && bitmap && eflags && vprefix && fprefix && n > 0 && capacity > 0 &&
+           !(capacity & (capacity - 1)) && capacity < (1ll << 31) && n <= capacity;
+}
+
+BF_API int bf_tsdf_surface_count(const void* keys, long long capacity, const int32_t* vox, const int64_t* skey,
+                                 const int* sslot, int n, int* rank_of_slot, void* bitmap, uint8_t* eflags, int* vprefix,
+                                 int* fprefix, int* totals, void* stream) {
+    if (!tsdf_surface_args(keys, capacity, skey, sslot, n, rank_of_slot, bitmap, eflags, vprefix, fprefix) || !vox || !totals)
+        return BF_ERR_ARG;
+    if ((long long)n * TSDF_VOX * 3 >= (1ll << 31)) return BF_ERR_CAPACITY;      // vertex and quad indices are int32
+    hipStream_t st = bf_stream(stream);
+    const u64 mask = (u64)(capacity - 1);
+    // -1 everywhere: an occupied block that the caller did not list has no vertices for its neighbours
+    if (hipMemsetAsync(rank_of_slot, 0xFF, (size_t)capacity * sizeof(int), st) != hipSuccess) return BF_ERR_LAUNCH;
+    hipLaunchKernelGGL(k_tsdf_cells<false>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
+                       (const long long*)skey, sslot, rank_of_slot, (u64*)bitmap, eflags, vprefix, 0.f, nullptr, nullptr);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, vprefix, n, 0, totals, 0);
+    hipLaunchKernelGGL(k_tsdf_faces<false>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
+                       (const int*)rank_of_slot, (const u64*)bitmap, (const uint8_t*)eflags, (const int*)vprefix, fprefix,
+                       nullptr);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, fprefix, n, 0, totals + 1, 0);
+    return bf_check_launch();
+}
+
+BF_API int bf_tsdf_surface_write(const void* keys, long long capacity, const int32_t* vox, const int64_t* skey,
+                                 const int* sslot, int n, const int* rank_of_slot, const void* bitmap, const uint8_t* eflags,
+                                 const int* vprefix, const int* fprefix, float voxel, float* verts, uint8_t* vrgb, int* faces,
+                                 void* stream) {
+    if (!tsdf_surface_args(keys, capacity, skey, sslot, n, rank_of_slot, bitmap, eflags, vprefix, fprefix) || !vox || !verts ||
+        !vrgb || !faces || !(voxel > 0.f))
+        return BF_ERR_ARG;
+    hipStream_t st = bf_stream(stream);
+    const u64 mask = (u64)(capacity - 1);
+    hipLaunchKernelGGL(k_tsdf_cells<true>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
+                       (const long long*)skey, sslot, (int*)rank_of_slot, (u64*)bitmap, (uint8_t*)eflags, (int*)vprefix, voxel,
+                       verts, vrgb);
+    hipLaunchKernelGGL(k_tsdf_faces<true>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
+                       rank_of_slot, (const u64*)bitmap, eflags, vprefix, (int*)fprefix, faces);
+    return bf_check_launch();
+}

@@ -96,6 +96,7 @@ class DetectStage:
         # the depth map's intrinsics (image K at 1/r, the synthetic CA-1M K_depth) for unproject
         Kd = self.K3.copy()
         Kd[:2] /= self.r
+        self.Kd3 = Kd
         self.Kd_dev = torch.from_numpy(np.stack([Kd] * batch)).to(self.dev)
         self.text = (text_features if text_features is not None else load_class_features()).to(self.dev).contiguous()
         names = class_names if class_names is not None else load_class_names()
@@ -289,7 +290,7 @@ class Pipeline:
         self.detect, self.fusion, self.gap = detect, fusion, gap
 
     def run(self, frames, n_frames, per_frame=True, frames_per_call=64, viz=None, cloud=None,
-            cloud_frames="keyframes", viz_points=False, snapshots=None):
+            cloud_frames="keyframes", viz_points=False, snapshots=None, mesh=None, mesh_frames="keyframes"):
         """frames(ids) -> (rgb [b,H,W,3] u8 dev, depth [b,H,W] f32 dev, poses [b,4,4] host).
         A frames callable that takes a `need_rgb` keyword is called with need_rgb=False for the
         non-keyframes whose RGB nothing reads (their per-frame work uses depth and pose only) and
@@ -308,20 +309,29 @@ class Pipeline:
         snapshots: a render.SnapshotWriter -- where viz gets the global boxes (after each keyframe's
         fusion step and after the last frame) it writes that frame's RGB with the boxes drawn over
         it as a PNG, and at the end the overviews of `cloud` (host side, like viz).
-        All four are off by default."""
+        mesh: a scene_mesh.TsdfVolume that fuses the depth (with the depth map's intrinsics, the
+        image's at 1 / depth_ratio), pose and colour of every keyframe
+        (mesh_frames="keyframes") or of every frame (mesh_frames="all", under cloud_frames="all"'s
+        conditions), enqueued on the current stream as soon as the frames are there.
+        All five are off by default."""
         if cloud_frames not in ("keyframes", "all"):
             raise ValueError("cloud_frames: 'keyframes' or 'all'")
+        if mesh_frames not in ("keyframes", "all"):
+            raise ValueError("mesh_frames: 'keyframes' or 'all'")
+        if mesh is not None and mesh_frames == "all" and not per_frame:
+            raise ValueError("mesh_frames='all' needs per_frame=True (the non-keyframes are read for it)")
         if cloud is not None and cloud_frames == "all" and not per_frame:
             raise ValueError("cloud_frames='all' needs per_frame=True (the non-keyframes' depth work)")
         viz_points = bool(viz_points) and viz is not None
         cloud_all = cloud is not None and cloud_frames == "all"
+        mesh_all = mesh is not None and mesh_frames == "all"
         B = self.detect.B
         kf = [i for i in range(n_frames) if i % self.gap == 0]
         try:
             lazy_rgb = "need_rgb" in inspect.signature(frames).parameters
         except (TypeError, ValueError):
             lazy_rgb = False
-        nk_rgb = (viz is not None and getattr(viz, "log_images", False)) or cloud_all or viz_points
+        nk_rgb = (viz is not None and getattr(viz, "log_images", False)) or cloud_all or viz_points or mesh_all
 
         def points(xyz, valid, rgb, n, integrate):
             # the first n frames' points: into the map, and / or as per-frame host rows for the viewer
@@ -345,6 +355,8 @@ class Pipeline:
                 nk = [i for i in range(ids[0], min(ids[-1] + self.gap, n_frames)) if i % self.gap != 0]
                 for c in range(0, len(nk), frames_per_call):
                     _rgb, depth, poses = nk_frames(nk[c:c + frames_per_call])
+                    if mesh_all:
+                        mesh.integrate(depth, self.detect.Kd3, poses, _rgb)
                     done = self.detect.preprocess_frames(depth.contiguous(), poses)
                     self.frames_preprocessed += len(nk[c:c + frames_per_call])
                     pts = None
@@ -356,6 +368,8 @@ class Pipeline:
                             if viz_points:
                                 nk_pose[i] += (pts[j],)
             rgb, depth, poses = frames(ids)
+            if mesh is not None:
+                mesh.integrate(depth, self.detect.Kd3, poses, rgb)
             if len(ids) < B:   # ragged tail: pad the batch with the last frame, drop its results
                 pad = B - len(ids)
                 rgb = torch.cat([rgb, rgb[-1:].expand(pad, -1, -1, -1)])

@@ -7,8 +7,9 @@ color/*.jpg, depth/*.png, pose/*.txt tree.
 of `DecodedFrameStream` for the exported tree of the same scene, the colour frames through
 bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zlib on the host);
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
-the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud and `... render
-scene.sens OUT_DIR [--boxes SEQ_boxes.pkl]` orbit and top-down PNG views of it (no model needed).
+the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
+scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume) and `... render
+scene.sens OUT_DIR [--boxes SEQ_boxes.pkl]` orbit and top-down PNG views of the cloud (no model needed).
 
 Layout (little-endian, packed): uint32 version (4), uint64 n + n bytes sensor name, four row-major
 4x4 float32 matrices (colour intrinsics / extrinsics, depth intrinsics / extrinsics), int32 colour
@@ -294,6 +295,33 @@ def cloud(sens, voxel=0.02, start=0, stop=None, step=1, max_depth=10.0, capacity
     return sc
 
 
+def mesh(sens, voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth=10.0, capacity=1 << 16, device="cuda",
+         batch=16):
+    """the scene as a TSDF: every selected frame through SensFrameStream, its depth with gt.depth.K, its
+    image and its pose as the file has it, `batch` frames per call, into a scene_mesh.TsdfVolume
+    (returned); frames without tracking (a -inf pose) are skipped and counted by the volume"""
+    import torch
+    from boxfusion_amd.scene_mesh import TsdfVolume
+    vol = TsdfVolume(voxel=voxel, trunc_voxels=trunc_voxels, capacity=capacity, max_depth=max_depth, device=device)
+    stream = SensFrameStream(sens, device=device, batch=batch, start=start, stop=stop, step=step)
+    poses = stream.sens.poses                      # as written, -inf included (the stream's are filled)
+    held = []
+
+    def flush():
+        if held:
+            vol.integrate(torch.stack([h[0] for h in held]), held[0][1], np.stack([h[2] for h in held]),
+                          torch.stack([h[3] for h in held]))
+            held.clear()
+    for sample in stream:
+        gt = sample["sensor_info"].gt
+        held.append((sample["wide"]["depth"][-1], gt.depth.K[-1], poses[sample["meta"]["timestamp"]],
+                     sample["wide"]["image"][-1].permute(1, 2, 0).contiguous()))
+        if len(held) == batch:
+            flush()
+    flush()
+    return vol
+
+
 def _cloud_arguments(p):
     p.add_argument("--voxel", type=float, default=0.02, help="voxel edge in metres")
     p.add_argument("--start", type=int, default=0)
@@ -319,6 +347,11 @@ def parser():
     pc.add_argument("sens")
     pc.add_argument("out")
     _cloud_arguments(pc)
+    pm = sub.add_parser("mesh", help="write the scene's surface (a TSDF of the depth frames) as a PLY")
+    pm.add_argument("sens")
+    pm.add_argument("out")
+    from boxfusion_amd.scene_mesh import add_volume_arguments
+    add_volume_arguments(pm)
     pr = sub.add_parser("render", help="write orbit and top-down PNG views of the scene's point cloud (and boxes)")
     pr.add_argument("sens")
     pr.add_argument("out", help="the directory of overview_<k>.png and overview_top.png")
@@ -340,6 +373,11 @@ def main(argv=None):
     if a.cmd == "render":
         from boxfusion_amd import render
         render.check_render_arguments(p, a)
+    if a.cmd == "mesh":
+        from boxfusion_amd.scene_mesh import check_volume_arguments
+        check_volume_arguments(p, a)
+        if not os.path.isfile(a.sens):
+            p.error(f"{a.sens} is missing")
     with SensFile(a.sens) as s:
         if a.cmd == "info":
             info(s)
@@ -348,6 +386,11 @@ def main(argv=None):
             n = sc.save_ply(a.out)
             print(f"{n} points -> {a.out}")
             print(" ".join(f"{k}={v}" for k, v in sc.stats().items()))
+        elif a.cmd == "mesh":
+            vol = mesh(s, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth, a.capacity)
+            nv, nf = vol.save_ply(a.out)
+            print(f"{nv} vertices, {nf} faces -> {a.out}")
+            print(vol.stats_line())
         elif a.cmd == "render":
             sc = cloud(s, a.voxel, a.start, a.stop, a.step, a.max_depth)
             paths = render.write_overviews(sc, render.load_boxes_argument(a.boxes), a.out, views=a.views, size=a.size,

@@ -247,6 +247,34 @@ def points_to_ply(xyz, rgb, path):
         fh.write(v.tobytes())
 
 
+def mesh_to_ply(xyz, rgb, faces, path):
+    """a coloured triangle mesh (xyz [n,3] float, rgb [n,3] u8, faces [m,3] int) as a binary
+    little-endian PLY: points_to_ply's vertex element, then a face element (list uchar int
+    vertex_indices), so whatever reads the points of a points_to_ply file reads this one's vertices"""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    if len(xyz) != len(rgb):
+        raise ValueError(f"mesh_to_ply: {len(xyz)} positions, {len(rgb)} colours")
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(xyz)):
+        raise ValueError(f"mesh_to_ply: face indices outside 0..{len(xyz) - 1}")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    v = np.empty(len(xyz), _POINT_DT)
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    f = np.empty(len(faces), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    f["n"] = 3
+    f["i"] = faces
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(f.tobytes())
+
+
 def read_ply_points(path):
     """the positions f32 [n,3] and colours u8 [n,3] of a PLY written by points_to_ply"""
     with open(path, "rb") as fh:

@@ -678,6 +678,71 @@ int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint8_t* rg
 int bf_cloud_extract(const void* table, long long capacity, int64_t* key, uint32_t* count,
                      uint32_t* sums, int* n_out, int* block_counts, void* stream);
 
+/* ---- scene mesh (the reference's data layout has mesh.ply, "Reconstructed 3D mesh", and leaves
+ * making it to open3d, data_process/README.md:48; here a TSDF volume on the device and surface nets) ----
+ *
+ * The volume is three arrays over `capacity` slots (a power of two below 2^31), one slot per block of
+ * 8x8x8 voxels: keys uint64 [capacity] (the block's three indices floor(x / (8 * voxel)) biased by
+ * 2^20, 21 bits each, x highest; all ones = empty), touched uint64 [capacity] (zero between calls)
+ * and vox int32 [capacity,6,512]: for voxel x + 8 y + 64 z of the block the observation count w,
+ * the sum of q = rint(min(sdf / trunc, 1) * 1024), the coloured-observation count cw, and the sums of
+ * r, g, b.  stats: uint64 [8], added to: voxel observations, frames skipped for a non-finite pose,
+ * ray samples whose block index lies outside +-2^20, probes that found neither the block nor an empty
+ * slot in capacity steps, observations refused by a voxel at max_weight, blocks claimed, 0, 0.
+ *
+ * bf_tsdf_touch: depth f32 [B,H,W] metres and poses f32 [B,4,4] camera-to-world of B <= 64 frames
+ * with one pinhole (fx, fy, cx, cy; pixel centres at integers).  A pixel is valid when
+ * 0 < d < max_depth.  Its ray is sampled at camera depths z = d + k * voxel, k = -trunc_voxels ..
+ * trunc_voxels: ((u - cx) * z / fx, (v - cy) * z / fy, z) through the pose, all f32 left to right;
+ * the sample's block is claimed and bit b of its touched word set.  A frame whose pose has a
+ * non-finite entry is skipped whole. */
+int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, int W, float fx, float fy,
+                  float cx, float cy, float voxel, int trunc_voxels, float max_depth, void* keys,
+                  void* touched, long long capacity, void* stats, void* stream);
+
+/* The slots with a non-zero touched word compacted into list (int32 [capacity]; *n_list int32 on the
+ * device; block_counts: int32 [bf_cloud_blocks(capacity, 1)] scratch), then per such block and per
+ * voxel centre p = (i + 0.5) * voxel, for every frame b whose bit is set: pc = R^T (p - t); z > 0;
+ * pixel (floor(fx x / z + cx + 0.5), floor(fy y / z + cy + 0.5)) inside the image with a valid
+ * depth d; sdf = d - z >= -trunc (trunc = trunc_voxels * voxel): w += 1, sum q += q, and if rgb (u8
+ * [B,H,W,3], may be null) and sdf <= trunc the colour sums and cw.  A voxel with w == max_weight
+ * (<= 2^20) refuses.  The touched words are zero again afterwards. */
+int bf_tsdf_update(const float* depth, const uint8_t* rgb, const float* poses, int B, int H, int W,
+                   float fx, float fy, float cx, float cy, float voxel, int trunc_voxels,
+                   float max_depth, int max_weight, const void* keys, void* touched, int32_t* vox,
+                   long long capacity, int* list, int* n_list, int* block_counts, void* stats,
+                   void* stream);
+
+/* the occupied slots in slot order: key int64 [capacity] and slot int32 [capacity], of which the
+ * first *n_out (int32, device) are written.  block_counts as above. */
+int bf_tsdf_extract(const void* keys, long long capacity, int64_t* key, int* slot, int* n_out,
+                    int* block_counts, void* stream);
+
+/* Naive surface nets over the n occupied blocks sorted by key (skey int64 [n], sslot int32 [n]).  A
+ * cell is the cube between eight neighbouring voxel centres and belongs to the block of its minimum
+ * corner; it is valid when all corners have w > 0; a corner's value is s = (float)sum q / (float)w,
+ * inside when s < 0.  A valid cell with both signs gets a vertex: the mean of the crossings
+ * t = s_a / (s_a - s_b) of its sign-changing edges (four along x, four along y, four along z), in
+ * voxels from the minimum corner's centre, coloured with the rounded mean of its coloured corners'
+ * rounded mean colours (grey 128 without any).  A sign-changing grid edge whose four cells have
+ * vertices gets a quad, split into two triangles whose normal points from the inside corner to the
+ * outside one.  Vertices are ordered by (block key, cell), triangles by (block key, cell, axis).
+ * _count fills the scratch (rank_of_slot int32 [capacity]: a listed slot's position in skey, -1 for
+ * every other slot -- an occupied block that is not listed still lends its samples to the listed
+ * blocks' cells, but has no vertices, and a quad that would need one is left out;
+ * bitmap uint64 [n,8], eflags u8 [n,512], vprefix / fprefix int32 [n]) and totals int32 [2] on the
+ * device: vertices, quads.  _write then
+ * writes verts f32 [totals[0],3], vrgb u8 [totals[0],3] and faces int32 [2 * totals[1],3]. */
+int bf_tsdf_surface_count(const void* keys, long long capacity, const int32_t* vox,
+                          const int64_t* skey, const int* sslot, int n, int* rank_of_slot,
+                          void* bitmap, uint8_t* eflags, int* vprefix, int* fprefix, int* totals,
+                          void* stream);
+int bf_tsdf_surface_write(const void* keys, long long capacity, const int32_t* vox,
+                          const int64_t* skey, const int* sslot, int n, const int* rank_of_slot,
+                          const void* bitmap, const uint8_t* eflags, const int* vprefix,
+                          const int* fprefix, float voxel, float* verts, uint8_t* vrgb, int* faces,
+                          void* stream);
+
 /* ---- headless renderer (the reference shows the scene and the boxes in the rerun viewer, demo.py:35-65;
  * here a z-buffer on the device draws them) ----
  *
