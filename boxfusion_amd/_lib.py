@@ -1474,6 +1474,41 @@ def render_edges(keys, corners, colors, mask, cams, intr, near, half_width, laye
                                  _ptr(keys), _stream()), "bf_render_edges")
 
 
+RENDER_COOP_PIXELS = 64       # DESIGN.md §4 "Renderer": the sweep of scripts/render_mesh_probe.py
+
+
+def _render_triangles_work(keys, vertices, rgb, faces, cams, intr, near, far, cull, shade, layer, coop_pixels=None,
+                           stats=None):
+    m, V = int(faces.shape[0]), int(keys.shape[0])
+    # algorithmic bytes: a face and its three vertices once per view; the pixels depend on the geometry
+    return dict(kind="render_triangles", m=m, views=V), 0.0, float(m) * V * (12 + 3 * 15)
+
+
+@_timed(_render_triangles_work)
+def render_triangles(keys, vertices, rgb, faces, cams, intr, near, far, cull, shade, layer, coop_pixels=None, stats=None):
+    """vertices f32 [n,3] / rgb u8 [n,3] / faces int32 [m,3] filled into keys int64 [V,H,W]
+    (bf_render_triangles); cull / shade / layer 0 or 1; coop_pixels: None (RENDER_COOP_PIXELS) or the
+    rectangle size from which a triangle is filled by its whole wave (the image does not depend on
+    it); stats: None or int64 [6] added to (pairs drawn, dropped as not finite or outside near..far,
+    dropped by index or guard band, culled or of zero area, pixels covered, atomics issued)"""
+    V, H, W = _render_target("render_triangles", keys)
+    vertices = _need(vertices, torch.float32, "render_triangles: vertices").contiguous()
+    rgb = _need(rgb, torch.uint8, "render_triangles: rgb").contiguous()
+    faces = _need(faces, torch.int32, "render_triangles: faces").contiguous()
+    n, m = vertices.shape[0], faces.shape[0]
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or tuple(rgb.shape) != (n, 3) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise HipError(f"render_triangles: vertices [n,3], rgb [n,3] and faces [m,3], got {tuple(vertices.shape)}, "
+                       f"{tuple(rgb.shape)} and {tuple(faces.shape)}")
+    if stats is not None and (_need(stats, torch.int64, "render_triangles: stats").numel() < 6):
+        raise HipError("render_triangles: stats int64 [6]")
+    cams, (fx, fy, cx, cy) = _render_cams("render_triangles", cams, V, intr)
+    coop = RENDER_COOP_PIXELS if coop_pixels is None else min(int(coop_pixels), 2 ** 31 - 1)
+    _check(lib().bf_render_triangles(_ptr(vertices), _ptr(rgb), ctypes.c_longlong(n), _ptr(faces), ctypes.c_longlong(m),
+                                     _ptr(cams), c_int(V), fx, fy, cx, cy, c_int(H), c_int(W), c_float(float(near)),
+                                     c_float(float(far)), c_int(int(cull)), c_int(int(shade)), c_int(int(layer)),
+                                     c_int(coop), _ptr(keys), _ptr(stats), _stream()), "bf_render_triangles")
+
+
 def _render_resolve_work(keys, background=(0, 0, 0)):
     return dict(kind="render_resolve", pixels=int(keys.numel())), 0.0, float(keys.numel()) * (8 + 3 + 4)
 

@@ -312,7 +312,8 @@ class Pipeline:
         mesh: a scene_mesh.TsdfVolume that fuses the depth (with the depth map's intrinsics, the
         image's at 1 / depth_ratio), pose and colour of every keyframe
         (mesh_frames="keyframes") or of every frame (mesh_frames="all", under cloud_frames="all"'s
-        conditions), enqueued on the current stream as soon as the frames are there.
+        conditions), enqueued on the current stream as soon as the frames are there.  A run given
+        both mesh and snapshots hands the volume to snapshots.finish, which also draws its surface.
         All five are off by default."""
         if cloud_frames not in ("keyframes", "all"):
             raise ValueError("cloud_frames: 'keyframes' or 'all'")
@@ -405,5 +406,8 @@ class Pipeline:
             if snapshots is not None:
                 snapshots.snapshot(last, p[0], last_rgb[0], self.fusion.all_pred_box)
         if snapshots is not None:
-            snapshots.finish(cloud, self.fusion.all_pred_box)
+            if mesh is not None:
+                snapshots.finish(cloud, self.fusion.all_pred_box, mesh=mesh)
+            else:
+                snapshots.finish(cloud, self.fusion.all_pred_box)
         return self.fusion

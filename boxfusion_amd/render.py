@@ -2,15 +2,17 @@
 
 The reference shows its scene in the rerun viewer (demo.py:35-65: a 3-D view, and the camera image
 with the boxes on it); a headless node has no viewer.  `Renderer` is a small z-buffer on the device
-(bf_render.hip): points and oriented-box wireframes become 64-bit keys (layer, depth bits, colour)
-that an atomicMin per pixel sorts, for several cameras at once, so the picture is the same bits
-whatever order the primitives arrive in (DESIGN.md §4 "Renderer").  `render_scene` draws a cloud and
-boxes from given cameras, `orbit_poses` / `topdown_pose` place cameras around a bounding box,
-`SnapshotWriter` is what `Pipeline.run(snapshots=...)` calls, and
+(bf_render.hip): points, oriented-box wireframes and filled, shaded triangles become 64-bit keys
+(layer, depth bits, colour) that an atomicMin per pixel sorts, for several cameras at once, so the
+picture is the same bits whatever order the primitives arrive in (DESIGN.md §4 "Renderer").
+`render_scene` draws a mesh, a cloud and boxes from given cameras, `orbit_poses` / `topdown_pose`
+place cameras around a bounding box, `SnapshotWriter` is what `Pipeline.run(snapshots=...)` calls, and
 
-    python -m boxfusion_amd.render CLOUD.ply OUT_DIR [--boxes SEQ_boxes.pkl] [--views 8] [--size H W]
+    python -m boxfusion_amd.render SCENE.ply OUT_DIR [--boxes SEQ_boxes.pkl] [--views 8] [--size H W]
+                                   [--as-points] [--no-cull] [--no-shade]
 
-writes the orbit and top-down views of any point PLY this package writes.
+writes the orbit and top-down views of any PLY this package writes: a PLY with faces (scene_mesh) as
+a surface, one without as points.
 """
 from __future__ import annotations
 
@@ -24,6 +26,7 @@ from boxfusion_amd import _lib
 from boxfusion_amd.synthetic import SCANNET_K
 
 MAX_RADIUS, MAX_HALF_WIDTH = 4, 2
+MESH_GREY = 128
 
 
 def camera_rows(poses):
@@ -100,6 +103,32 @@ class Renderer:
             mask = (mask != 0).reshape(-1)
         _lib.render_edges(self.keys, corners, colors, mask, self._cams(poses), self.intr, near, half_width,
                           0 if xray else 1)
+
+    def draw_mesh(self, vertices, faces, rgb_u8=None, poses=None, shade=True, cull=False, near=0.05, far=20.0,
+                  overlay=False, stats=None, coop_pixels=None):
+        """the triangles faces int [m,3] of vertices [n,3] float (host or device), filled and
+        depth-tested, the colours rgb_u8 [n,3] uint8 (None: mid-grey) interpolated between the
+        vertices; shade: a two-sided headlight; cull: drop the triangles seen from behind (the side a
+        scene_mesh surface was not observed from).  A triangle with a vertex outside near < Z < far is
+        dropped whole: there is no near-plane clipping.  stats: None or int64 [6] on the device
+        (_lib.render_triangles)"""
+        if poses is None:
+            raise ValueError("draw_mesh: poses")
+        vertices = self._dev(vertices, torch.float32, (3,), "vertices")
+        if rgb_u8 is None:
+            rgb = torch.full((vertices.shape[0], 3), MESH_GREY, dtype=torch.uint8, device=self.device)
+        else:
+            rgb = self._dev(rgb_u8, torch.uint8, (3,), "rgb_u8")
+        t = faces if torch.is_tensor(faces) else torch.from_numpy(np.ascontiguousarray(faces))
+        if t.dtype not in (torch.int32, torch.int64) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"faces: an integer [m,3], got {t.dtype} {tuple(t.shape)}")
+        if t.dtype == torch.int64:                               # an index beyond int32 is a bad index: -1 is one
+            t = torch.where((t >= 0) & (t < 2 ** 31), t, torch.full_like(t, -1)).to(torch.int32)
+        faces = t.to(self.device).contiguous()
+        if vertices.shape[0] != rgb.shape[0]:
+            raise ValueError(f"draw_mesh: {vertices.shape[0]} vertices, {rgb.shape[0]} colours")
+        _lib.render_triangles(self.keys, vertices, rgb, faces, self._cams(poses), self.intr, near, far, 1 if cull else 0,
+                              1 if shade else 0, 0 if overlay else 1, coop_pixels=coop_pixels, stats=stats)
 
     def resolve(self, background=(0, 0, 0)):
         """-> (rgb u8 [views,H,W,3], depth f32 [views,H,W]) on the device; empty pixels take the
@@ -200,14 +229,27 @@ def _boxes_of(boxes):
     return corners, (box_colors(n) if colors is None else colors)
 
 
+def _mesh_of(mesh):
+    if mesh is None:
+        return None
+    if hasattr(mesh, "mesh") and callable(mesh.mesh):                # a TsdfVolume
+        return mesh.mesh()
+    vertices, rgb, faces = mesh
+    return vertices, rgb, faces
+
+
 def render_scene(points, boxes, poses, K3, H, W, radius=1, half_width=1, xray=False, background=(0, 0, 0),
-                 near=0.05, far=100.0, device="cuda"):
+                 near=0.05, far=100.0, device="cuda", mesh=None, shade=True, cull=False):
     """points: a SceneCloud, an (xyz [n,3], rgb u8 [n,3]) pair or None; boxes: corners [B,8,3], a
-    (corners, colours u8 [B,3]) pair or None (default colours: box_colors); poses: camera -> world
-    [V,4,4] -> (rgb u8 [V,H,W,3], depth f32 [V,H,W]) on the device"""
+    (corners, colours u8 [B,3]) pair or None (default colours: box_colors); mesh: a TsdfVolume, a
+    (vertices [n,3], rgb u8 [n,3] or None, faces [m,3]) triple or None, drawn filled (shade, cull:
+    Renderer.draw_mesh); poses: camera -> world [V,4,4] -> (rgb u8 [V,H,W,3], depth f32 [V,H,W]) on
+    the device"""
     rows = camera_rows(poses)
     r = Renderer(H, W, K3, views=rows.shape[0], device=device)
-    pts, bx = _points_of(points), _boxes_of(boxes)
+    pts, bx, tri = _points_of(points), _boxes_of(boxes), _mesh_of(mesh)
+    if tri is not None:
+        r.draw_mesh(tri[0], tri[2], tri[1], poses, shade=shade, cull=cull, near=near, far=far)
     if pts is not None:
         r.draw_points(pts[0], pts[1], poses, radius=radius, near=near, far=far)
     if bx is not None:
@@ -227,8 +269,11 @@ def save_png(rgb_u8, path):
     Image.fromarray(rgb_u8).save(path, format="PNG")
 
 
-def _bounds(xyz, boxes):
+def _bounds(xyz, boxes, vertices=None):
     parts = []
+    if vertices is not None and len(vertices):
+        x = vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else np.asarray(vertices)
+        parts.append(x.reshape(-1, 3))
     if xyz is not None and len(xyz):
         x = xyz.detach().cpu().numpy() if torch.is_tensor(xyz) else np.asarray(xyz)
         parts.append(x.reshape(-1, 3))
@@ -242,18 +287,22 @@ def _bounds(xyz, boxes):
     return pts.min(0), pts.max(0)
 
 
-def write_overviews(points, boxes, out_dir, views=8, size=(480, 640), radius=1, half_width=1, K3=None, device="cuda"):
-    """`views` orbit views (overview_<k>.png) and one from above (overview_top.png) of a cloud and
-    depth-tested boxes, the cameras placed around what is drawn; returns the paths written"""
+def write_overviews(points, boxes, out_dir, views=8, size=(480, 640), radius=1, half_width=1, K3=None, device="cuda",
+                    mesh=None, shade=True, cull=True, prefix="overview"):
+    """`views` orbit views (<prefix>_<k>.png) and one from above (<prefix>_top.png) of a cloud, a
+    mesh and depth-tested boxes, the cameras placed around what is drawn; returns the paths written.
+    A mesh is drawn culled by default: the orbit cameras stand outside a room whose walls face
+    inwards, so culling shows the doll's house rather than the outside of four walls"""
     H, W = int(size[0]), int(size[1])
     K3 = overview_K(H, W) if K3 is None else K3
-    pts, bx = _points_of(points), _boxes_of(boxes)
-    lo, hi = _bounds(None if pts is None else pts[0], bx)
+    pts, bx, tri = _points_of(points), _boxes_of(boxes), _mesh_of(mesh)
+    lo, hi = _bounds(None if pts is None else pts[0], bx, None if tri is None else tri[0])
     poses = np.concatenate([orbit_poses(lo, hi, views, K3=K3, H=H, W=W), topdown_pose(lo, hi, K3, H, W)[None]])
     far = 4.0 * float(np.linalg.norm(hi - lo)) + 10.0
-    rgb, _ = render_scene(pts, bx, poses, K3, H, W, radius=radius, half_width=half_width, far=far, device=device)
+    rgb, _ = render_scene(pts, bx, poses, K3, H, W, radius=radius, half_width=half_width, far=far, device=device,
+                          mesh=tri, shade=shade, cull=cull)
     rgb = rgb.cpu().numpy()
-    names = [f"overview_{k}.png" for k in range(int(views))] + ["overview_top.png"]
+    names = [f"{prefix}_{k}.png" for k in range(int(views))] + [f"{prefix}_top.png"]
     paths = [os.path.join(out_dir, n) for n in names]
     for img, p in zip(rgb, paths):
         save_png(img, p)
@@ -264,7 +313,8 @@ class SnapshotWriter:
     """What Pipeline.run(snapshots=...) calls: after every keyframe's fusion step (and after the last
     frame) `snap_<count:06d>.png`, the frame's RGB with the current global boxes as x-ray wireframes
     from the frame's camera; at the end, when the run also filled a SceneCloud and cloud_views > 0,
-    `overview_<k>.png` and `overview_top.png` of the cloud with depth-tested boxes."""
+    `overview_<k>.png` and `overview_top.png` of the cloud with depth-tested boxes, and, when finish
+    is given the run's TsdfVolume, `mesh_<k>.png` and `mesh_top.png` of its surface with them."""
 
     def __init__(self, out_dir, K3, H, W, every="keyframes", cloud_views=0, half_width=1, device="cuda"):
         if every != "keyframes":
@@ -298,11 +348,17 @@ class SnapshotWriter:
         self.written.append(path)
         return path
 
-    def finish(self, cloud, all_pred_box):
-        if cloud is None or self.cloud_views <= 0:
+    def finish(self, cloud, all_pred_box, mesh=None):
+        if self.cloud_views <= 0:
             return []
-        paths = write_overviews(cloud, self._corners(all_pred_box), self.out_dir, views=self.cloud_views,
-                                size=(self.H, self.W), half_width=self.half_width, device=self.device)
+        paths = []
+        if cloud is not None:
+            paths += write_overviews(cloud, self._corners(all_pred_box), self.out_dir, views=self.cloud_views,
+                                     size=(self.H, self.W), half_width=self.half_width, device=self.device)
+        if mesh is not None:
+            paths += write_overviews(None, self._corners(all_pred_box), self.out_dir, views=self.cloud_views,
+                                     size=(self.H, self.W), half_width=self.half_width, device=self.device, mesh=mesh,
+                                     prefix="mesh")
         self.written += paths
         return paths
 
@@ -313,6 +369,8 @@ def add_render_arguments(p):
     p.add_argument("--views", type=int, default=8, help="orbit views")
     p.add_argument("--size", type=int, nargs=2, default=[480, 640], metavar=("H", "W"))
     p.add_argument("--radius", type=int, default=1, help=f"point splat radius in pixels, 0..{MAX_RADIUS}")
+    p.add_argument("--no-cull", action="store_true", help="a mesh: also draw the triangles seen from behind")
+    p.add_argument("--no-shade", action="store_true", help="a mesh: the vertex colours as they are, no headlight")
 
 
 def check_render_arguments(p, a):
@@ -332,19 +390,26 @@ def load_boxes_argument(path):
 def parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m boxfusion_amd.render",
-                                description="orbit and top-down PNG views of a point PLY (and boxes)")
-    p.add_argument("cloud", help="a point PLY written by SceneCloud.save_ply / visualize.points_to_ply")
+                                description="orbit and top-down PNG views of a point or mesh PLY (and boxes)")
+    p.add_argument("cloud", help="a PLY written by SceneCloud.save_ply / visualize.points_to_ply (points) or "
+                                 "TsdfVolume.save_ply / visualize.mesh_to_ply (drawn as a surface)")
     p.add_argument("out_dir")
     add_render_arguments(p)
+    p.add_argument("--as-points", action="store_true", help="draw a mesh PLY's vertices as points")
     return p
 
 
 def main(argv=None):
-    from boxfusion_amd.visualize import read_ply_points
+    from boxfusion_amd.visualize import read_ply_surface
     p = parser()
     a = p.parse_args(argv)
     check_render_arguments(p, a)
-    xyz, rgb = read_ply_points(a.cloud)
+    xyz, rgb, faces = read_ply_surface(a.cloud)
+    if len(faces) and not a.as_points:
+        paths = write_overviews(None, load_boxes_argument(a.boxes), a.out_dir, views=a.views, size=a.size,
+                                mesh=(xyz, rgb, faces), shade=not a.no_shade, cull=not a.no_cull)
+        print(f"{len(xyz)} vertices, {len(faces)} faces -> {len(paths)} views in {a.out_dir}")
+        return 0
     paths = write_overviews((xyz, rgb), load_boxes_argument(a.boxes), a.out_dir, views=a.views, size=a.size, radius=a.radius)
     print(f"{len(xyz)} points -> {len(paths)} views in {a.out_dir}")
     return 0

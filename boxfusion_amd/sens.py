@@ -9,7 +9,8 @@ bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zl
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
 the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
 scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume) and `... render
-scene.sens OUT_DIR [--boxes SEQ_boxes.pkl]` orbit and top-down PNG views of the cloud (no model needed).
+scene.sens OUT_DIR [--boxes SEQ_boxes.pkl] [--mesh]` orbit and top-down PNG views of the cloud, or with
+--mesh of the TSDF surface (no model needed).
 
 Layout (little-endian, packed): uint32 version (4), uint64 n + n bytes sensor name, four row-major
 4x4 float32 matrices (colour intrinsics / extrinsics, depth intrinsics / extrinsics), int32 colour
@@ -357,6 +358,10 @@ def parser():
     pr.add_argument("out", help="the directory of overview_<k>.png and overview_top.png")
     _cloud_arguments(pr)
     add_render_arguments(pr)
+    pr.add_argument("--mesh", action="store_true",
+                    help="fuse the depth frames into a TSDF and draw its surface instead of the point cloud")
+    pr.add_argument("--trunc-voxels", type=int, default=4, help="--mesh: truncation distance in voxels")
+    pr.add_argument("--capacity", type=int, default=1 << 16, help="--mesh: blocks of 8x8x8 voxels, a power of two")
     return p
 
 
@@ -373,6 +378,9 @@ def main(argv=None):
     if a.cmd == "render":
         from boxfusion_amd import render
         render.check_render_arguments(p, a)
+        if a.mesh:
+            from boxfusion_amd.scene_mesh import check_volume_arguments
+            check_volume_arguments(p, a)
     if a.cmd == "mesh":
         from boxfusion_amd.scene_mesh import check_volume_arguments
         check_volume_arguments(p, a)
@@ -391,6 +399,11 @@ def main(argv=None):
             nv, nf = vol.save_ply(a.out)
             print(f"{nv} vertices, {nf} faces -> {a.out}")
             print(vol.stats_line())
+        elif a.cmd == "render" and a.mesh:
+            vol = mesh(s, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth, a.capacity)
+            paths = render.write_overviews(None, render.load_boxes_argument(a.boxes), a.out, views=a.views, size=a.size,
+                                           mesh=vol, shade=not a.no_shade, cull=not a.no_cull)
+            print(f"{vol.stats_line()} -> {len(paths)} views in {a.out}")
         elif a.cmd == "render":
             sc = cloud(s, a.voxel, a.start, a.stop, a.step, a.max_depth)
             paths = render.write_overviews(sc, render.load_boxes_argument(a.boxes), a.out, views=a.views, size=a.size,

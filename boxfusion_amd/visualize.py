@@ -287,6 +287,27 @@ def read_ply_points(path):
             np.stack([v["red"], v["green"], v["blue"]], 1).reshape(-1, 3))
 
 
+def read_ply_surface(path):
+    """(positions f32 [n,3], colours u8 [n,3], faces int32 [m,3]) of any binary PLY this module
+    writes: float vertices (points_to_ply, mesh_to_ply) or double ones (boxes3d_to_ply), with a
+    triangle face element or without one (m = 0)"""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    count = lambda name: [int(h.split()[-1]) for h in head if h.startswith("element " + name)]
+    nv, nf = count("vertex")[0], (count("face") or [0])[0]
+    real = "<f8" if "property double x" in head else "<f4"
+    vdt = np.dtype([("x", real), ("y", real), ("z", real), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    v = np.frombuffer(data, vdt, nv, end)
+    f = np.frombuffer(data, fdt, nf, end + nv * vdt.itemsize)
+    if nf and (f["n"] != 3).any():
+        raise ValueError(f"{path}: faces that are not triangles")
+    return (np.stack([v["x"], v["y"], v["z"]], 1).reshape(-1, 3).astype(np.float32),
+            np.stack([v["red"], v["green"], v["blue"]], 1).reshape(-1, 3), f["i"].reshape(-1, 3).astype(np.int32))
+
+
 class FrameLogger:
     """demo.py:93-197's per-frame log calls in the reference's order: set_time, camera pose +
     pinhole on /world/image and /device/wide/image, the RGB image, the depth image and its

@@ -776,6 +776,29 @@ int bf_render_edges(const float* corners, const uint8_t* colors, const uint8_t* 
                     int V, float fx, float fy, float cx, float cy, int H, int W, float near_z, int half_width,
                     int layer, void* keys, void* stream);
 
+/* m triangles (vertices f32 [n,3], rgb u8 [n,3] per vertex, faces int32 [m,3]) filled into every view,
+ * watertight: a pixel inside a closed surface is covered by exactly one of the triangles that share an edge
+ * or a vertex there.  Per (triangle, view), dropped whole when a face index is outside 0..n-1, a vertex or
+ * its camera-space image is not finite, any vertex fails near_z < Z < far_z (no near-plane clipping), any
+ * projected |u| or |v| is >= 2^22, or the snapped area is zero.  u, v as for points; xs = (int)rintf(u *
+ * 256), ys alike (pixel (ix, iy) has its centre at (256 ix, 256 iy)).  area2 = (x1 - x0)(y2 - y0) - (y1 -
+ * y0)(x2 - x0) in int64; cull = 1 drops area2 > 0 (the back of bf_tsdf_surface_write's faces: the side the
+ * depth was not seen from); else area2 < 0 swaps vertices 1 and 2.  Pixels ceil(min xs / 256) .. floor(max
+ * xs / 256) (rows alike), clipped to the image.  Edge i runs from a = (i+1) % 3 to b = (i+2) % 3: dx = xb -
+ * xa, dy = yb - ya, E_i = dx (py - ya) - dy (px - xa) in int64; covered when every E_i > 0, or E_i == 0 and
+ * (dy < 0 or (dy == 0 and dx > 0)).  In f64: t_i = (double)E_i * (1.0 / (double)Z_i), iw = (t0 + t1) + t2, r
+ * = 1.0 / iw, Z = (float)((double)area2 * r), channel = ((t0 c0 + t1 c1) + t2 c2) * r, times (double)s when
+ * shade = 1, rint, clamped to 0..255.  s (f32) = 0.3 + 0.7 min(|n . g| / sqrt((n . n) (g . g)), 1), n = (P1 - P0) x (P2 -
+ * P0), g = (P0 + P1) + P2 in camera space, 0.3 when the quotient is not finite.  coop_pixels >= 0: a
+ * triangle whose clipped pixel rectangle has fewer pixels is filled by its own lane, the others by their
+ * whole wave, one at a time; the image does not depend on it.  stats: NULL, or uint64 [6] added to:
+ * (triangle, view) pairs drawn, dropped as not finite or outside near..far, dropped by index or the 2^22
+ * bound, culled or of zero area, pixels covered, atomics issued. */
+int bf_render_triangles(const float* vertices, const uint8_t* rgb, long long n, const int32_t* faces, long long m,
+                        const float* cams, int V, float fx, float fy, float cx, float cy, int H, int W,
+                        float near_z, float far_z, int cull, int shade, int layer, int coop_pixels, void* keys,
+                        void* stats, void* stream);
+
 /* keys -> rgb u8 [V,H,W,3] and depth f32 [V,H,W] (the stored Z; 0 where empty).  An empty pixel takes
  * bg_image's pixel (u8 [V,H,W,3]) when that is not NULL, else the constant (bg_r, bg_g, bg_b). */
 int bf_render_resolve(const void* keys, int V, int H, int W, const uint8_t* bg_image, int bg_r, int bg_g,
