@@ -1397,6 +1397,119 @@ def tsdf_surface(keys, vox, skey, sslot, voxel):
     return verts, vrgb, faces[:2 * nq]
 
 
+TSDF_RAYCAST_STATS = ("hits", "behind", "left_range", "skipped_pose", "no_normal")
+
+
+def _tsdf_raycast_work(keys, vox, poses, intr, H, W, voxel, trunc_voxels, near, far, min_weight, max_steps, counters,
+                       colour=False):
+    n = float(poses.shape[0]) * H * W
+    return dict(kind="tsdf_raycast", n=int(n), colour=bool(colour)), 0.0, n * 28
+
+
+@_timed(_tsdf_raycast_work)
+def tsdf_raycast(keys, vox, poses, intr, H, W, voxel, trunc_voxels, near, far, min_weight, max_steps, counters,
+                 colour=False):
+    """the volume seen from poses f32 [V,4,4] through the pinhole intr at H x W (bf_tsdf_raycast):
+    (depth f32 [V,H,W], vertex f32 [V,H,W,3], normal f32 [V,H,W,3], rgb u8 [V,H,W,3] or None);
+    counters int64 [8] is added to (TSDF_RAYCAST_STATS)"""
+    _need(keys, torch.int64, "tsdf_raycast: keys")
+    poses = _need(poses, torch.float32, "tsdf_raycast: poses").contiguous()
+    cap, dev = keys.shape[0], keys.device
+    if keys.dim() != 1 or vox.dtype != torch.int32 or tuple(vox.shape) != (cap, TSDF_FIELDS, TSDF_VOX):
+        raise HipError("tsdf_raycast: keys [capacity] and vox int32 [capacity,6,512] of tsdf_volume")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
+        raise HipError(f"tsdf_raycast: poses [V,4,4], got {tuple(poses.shape)}")
+    if counters.dtype != torch.int64 or counters.numel() < 8:
+        raise HipError("tsdf_raycast: counters int64 [8]")
+    V, H, W = int(poses.shape[0]), int(H), int(W)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    vertex = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
+    normal = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
+    rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev) if colour else None
+    _check(lib().bf_tsdf_raycast(_ptr(keys), _ptr(vox), ctypes.c_longlong(cap), _ptr(poses), c_int(V), c_int(H), c_int(W),
+                                 *_intr4(intr), c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(near)),
+                                 c_float(float(far)), c_int(int(min_weight)), c_int(int(max_steps)), _ptr(depth),
+                                 _ptr(vertex), _ptr(normal), _ptr(rgb), _ptr(counters), _stream()), "bf_tsdf_raycast")
+    return depth, vertex, normal, rgb
+
+
+# ------------------------------------------------------------------------------------------
+# tracking (bf_track.hip)
+# ------------------------------------------------------------------------------------------
+def _depth_vertex_normal_work(depth, intr, max_depth, jump):
+    return dict(kind="depth_vertex_normal", n=int(depth.numel())), 0.0, float(depth.numel()) * 28
+
+
+@_timed(_depth_vertex_normal_work)
+def depth_vertex_normal(depth, intr, max_depth, jump):
+    """depth f32 [H,W] metres -> camera-frame (vertex f32 [H,W,3], normal f32 [H,W,3])
+    (bf_depth_vertex_normal)"""
+    depth = _need(depth, torch.float32, "depth_vertex_normal: depth").contiguous()
+    if depth.dim() != 2:
+        raise HipError(f"depth_vertex_normal: depth [H,W], got {tuple(depth.shape)}")
+    H, W = depth.shape
+    vertex = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
+    normal = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
+    _check(lib().bf_depth_vertex_normal(_ptr(depth), c_int(H), c_int(W), *_intr4(intr), c_float(float(max_depth)),
+                                        c_float(float(jump)), _ptr(vertex), _ptr(normal), _stream()),
+           "bf_depth_vertex_normal")
+    return vertex, normal
+
+
+def icp_blocks(H, W, stride):
+    """rows of bf_icp_reduce's partials for a live map of H x W sampled at `stride`"""
+    lib().bf_icp_blocks.restype = c_int
+    n = int(lib().bf_icp_blocks(c_int(int(H)), c_int(int(W)), c_int(int(stride))))
+    if n <= 0:
+        raise HipError(f"icp_blocks: H, W, stride = {H}, {W}, {stride}")
+    return n
+
+
+def _icp_reduce_work(live_vertex, live_normal, stride, T, model_vertex, model_normal, model_w2c, intr, dist_max, cos_min,
+                     out=None):
+    n = float(live_vertex.shape[0] // stride) * (live_vertex.shape[1] // stride)
+    return dict(kind="icp_reduce", n=int(n), stride=int(stride)), n * 120.0, n * 48.0
+
+
+@_timed(_icp_reduce_work)
+def icp_reduce(live_vertex, live_normal, stride, T, model_vertex, model_normal, model_w2c, intr, dist_max, cos_min,
+               out=None):
+    """the normal equations of one ICP iteration (bf_icp_reduce): out f64 [32] on the device = the 21
+    upper-triangle entries of J^T J, the 6 of J^T r, sum r^2, the inlier count.  live maps f32 [H,W,3]
+    (camera frame), T host f64 [3,4] camera-to-world, model maps f32 [Hm,Wm,3] (world) of the camera
+    model_w2c (host f64 [3,4]) with the pinhole intr"""
+    for t, name in ((live_vertex, "live_vertex"), (live_normal, "live_normal"), (model_vertex, "model_vertex"),
+                    (model_normal, "model_normal")):
+        _need(t, torch.float32, f"icp_reduce: {name}")
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise HipError(f"icp_reduce: {name} [H,W,3], got {tuple(t.shape)}")
+    if live_vertex.shape != live_normal.shape or model_vertex.shape != model_normal.shape:
+        raise HipError("icp_reduce: a vertex and a normal map of one size each")
+    stride = int(stride)
+    if stride < 1:
+        raise HipError("icp_reduce: stride >= 1")
+    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    M = np.ascontiguousarray(np.asarray(model_w2c, np.float64).reshape(-1)[:12])
+    if T.size != 12 or M.size != 12:
+        raise HipError("icp_reduce: T and model_w2c f64 [3,4]")
+    H, W = live_vertex.shape[:2]
+    Hm, Wm = model_vertex.shape[:2]
+    dev = live_vertex.device
+    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(32, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != 32:
+        raise HipError("icp_reduce: out f64 [32]")
+    dp = ctypes.POINTER(c_double)
+    fx, fy, cx, cy = (c_double(float(np.float32(v))) for v in intr)
+    _check(lib().bf_icp_reduce(_ptr(live_vertex.contiguous()), _ptr(live_normal.contiguous()), c_int(H), c_int(W),
+                               c_int(stride), T.ctypes.data_as(dp), _ptr(model_vertex.contiguous()),
+                               _ptr(model_normal.contiguous()), c_int(Hm), c_int(Wm), M.ctypes.data_as(dp), fx, fy, cx, cy,
+                               c_double(float(dist_max)), c_double(float(cos_min)), _ptr(partials), _ptr(out), _stream()),
+           "bf_icp_reduce")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # headless renderer (bf_render.hip)
 # ------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ SOURCES = {
     "bf_eval.hip": EXACT,
     "bf_render.hip": EXACT,
     "bf_tsdf.hip": EXACT,
+    "bf_track.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 

@@ -7,6 +7,8 @@
 //   bf_tsdf_extract        the occupied slots, compacted (in slot order)
 //   bf_tsdf_surface_count  over the key-sorted blocks: the cells that get a vertex, the grid edges that get a quad,
 //   bf_tsdf_surface_write  their scans, and the vertices / triangles written at the scanned positions
+//   bf_tsdf_raycast        the volume read back from a pose: one ray per pixel marched through the blocks to the
+//                          surface, as depth / vertex / normal / colour maps (what bf_track.hip aligns a frame to)
 // The volume is three arrays over `capacity` slots: keys u64 (three block indices biased by 2^20, 21 bits each;
 // all ones = empty), touched u64 (bit f = frame f of the launch in flight reaches this block) and vox
 // int32 [capacity, 6, 512]: per voxel (x fastest, then y, then z)
@@ -546,5 +548,245 @@ BF_API int bf_tsdf_surface_write(const void* keys, long long capacity, const int
                        verts, vrgb);
     hipLaunchKernelGGL(k_tsdf_faces<true>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
                        rank_of_slot, (const u64*)bitmap, eflags, vprefix, (int*)fprefix, faces);
+    return bf_check_launch();
+}
+
+// ---- raycast: the volume read back as a predicted depth / vertex / normal map ---------------------------------------------
+// One thread per pixel, one wave per 8 x 8 pixel tile (lane = x + 8 y), so that the rays of a wave stay in the same
+// blocks.  The ray of pixel (u, v) is o + d t with o the pose's translation, d = R (a, b, 1), a = (u - cx) / fx,
+// b = (v - cy) / fy, and t the depth in the camera; len = sqrt(a a + b b + 1) metres per unit of t.  All f32, left
+// to right, no contraction.
+//   field   s(p): g = p / voxel - 0.5, i = floor(g), f = g - i; the eight voxels i + (c & 1, (c >> 1) & 1, c >> 2) must
+//           all exist with w >= min_weight; their values (float)q / (float)w / 1024 are interpolated along x, then y,
+//           then z, each as lo + f * (hi - lo).
+//   step    t starts at near.  While t < far and fewer than max_steps steps were made:
+//           the block floor(p / (8 voxel)) is absent (or past the index range): t += max(min over the axes with
+//           d_i != 0 of (bound_i - p_i) / d_i, 0) + 0.25 voxel / len, bound_i the block's face the ray leaves through;
+//           the sample is forgotten.
+//           the block is present and s(p) invalid: t += voxel / len; the sample is forgotten.
+//           s(p) valid: t += max(0.5 |s| trunc, 0.25 voxel) / len -- at most half the truncation distance, at least a
+//           quarter voxel, so a surface as thin as the band cannot be stepped over.
+//   hit     s < 0 is inside and s >= 0 outside (zero is outside, as in the surface extractor).  The first step from a
+//           valid outside sample to the next sample, valid and inside, is the hit: t_hit = t0 + (t1 - t0) * s0 / (s0 - s1).
+//           A step from a valid inside sample to a valid outside one ends the ray: the camera is behind that surface.
+//   normal  the central differences of s at p_hit +- voxel / 2 along x, y, z, normalised; a pixel with an invalid tap or
+//           a zero gradient is no hit.
+// counters (u64 [8]): hits, rays ended behind a surface, rays that left the range (or ran out of steps), views
+// skipped for a non-finite pose, rays whose hit had no normal.
+enum { RC_HITS = 0, RC_BEHIND, RC_LEFT_RANGE, RC_SKIPPED_POSE, RC_NO_NORMAL };
+
+// the slot of block (bx, by, bz) as floats (whole numbers), through the lane's one-entry cache; -1: absent or out of range
+__device__ __forceinline__ int rc_block(const u64* __restrict__ keys, u64 mask, float bx, float by, float bz, u64& ckey,
+                                        int& cslot) {
+    const float lim = 1048576.0f;
+    if (!(bx >= -lim && bx < lim && by >= -lim && by < lim && bz >= -lim && bz < lim)) return -1;
+    const u64 key = ((u64)((int)bx + TSDF_BIAS) << 42) | ((u64)((int)by + TSDF_BIAS) << 21) | (u64)((int)bz + TSDF_BIAS);
+    if (key != ckey) {
+        ckey = key;
+        cslot = tsdf_lookup(keys, mask, key);
+    }
+    return cslot;
+}
+
+// the word index of voxel (ix, iy, iz)'s w, or -1
+__device__ __forceinline__ long long rc_voxel(const u64* __restrict__ keys, u64 mask, int ix, int iy, int iz, u64& ckey,
+                                              int& cslot) {
+    const u64 key = ((u64)((ix >> 3) + TSDF_BIAS) << 42) | ((u64)((iy >> 3) + TSDF_BIAS) << 21) | (u64)((iz >> 3) + TSDF_BIAS);
+    if (key != ckey) {
+        ckey = key;
+        cslot = tsdf_lookup(keys, mask, key);
+    }
+    if (cslot < 0) return -1;
+    return (long long)cslot * TSDF_BLOCK_WORDS + ((ix & 7) | ((iy & 7) << 3) | ((iz & 7) << 6));
+}
+
+__device__ __forceinline__ bool rc_sample(const u64* __restrict__ keys, u64 mask, const int* __restrict__ vox, float voxel,
+                                          int min_weight, float px, float py, float pz, u64& ckey, int& cslot, float* s) {
+    const float gx = px / voxel - 0.5f, gy = py / voxel - 0.5f, gz = pz / voxel - 0.5f;
+    const float x0 = floorf(gx), y0 = floorf(gy), z0 = floorf(gz);
+    const float lim = 8388600.0f;                                // below 2^23: every corner's block index is within 2^20
+    if (!(x0 >= -lim && x0 < lim && y0 >= -lim && y0 < lim && z0 >= -lim && z0 < lim)) return false;
+    const float tx = gx - x0, ty = gy - y0, tz = gz - z0;
+    const int ix = (int)x0, iy = (int)y0, iz = (int)z0;
+    float v[8];
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        v[c] = 0.f;
+        if (!ok) continue;
+        const long long at = rc_voxel(keys, mask, ix + (c & 1), iy + ((c >> 1) & 1), iz + (c >> 2), ckey, cslot);
+        if (at < 0) {
+            ok = false;
+            continue;
+        }
+        const int w = vox[at];
+        if (w < min_weight) {
+            ok = false;
+            continue;
+        }
+        v[c] = (float)vox[at + TSDF_VOX] / (float)w / 1024.0f;
+    }
+    if (!ok) return false;
+    const float c00 = v[0] + tx * (v[1] - v[0]), c10 = v[2] + tx * (v[3] - v[2]);
+    const float c01 = v[4] + tx * (v[5] - v[4]), c11 = v[6] + tx * (v[7] - v[6]);
+    const float c0 = c00 + ty * (c10 - c00), c1 = c01 + ty * (c11 - c01);
+    *s = c0 + tz * (c1 - c0);
+    return true;
+}
+
+__device__ __forceinline__ void rc_count(u64* counters, int which, bool flag) {
+    const u64 m = __ballot(flag);
+    if (m && bf_lane() == (int)(__ffsll((long long)m) - 1)) atomicAdd(counters + which, (u64)__popcll(m));
+}
+
+__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_raycast(const u64* __restrict__ keys, u64 mask, const int* __restrict__ vox,
+                                                              const float* __restrict__ poses, int H, int W, int tiles_x,
+                                                              int tiles, int bpv, float fx, float fy, float cx, float cy,
+                                                              float voxel, int T, float near_z, float far_z, int min_weight,
+                                                              int max_steps, float* __restrict__ depth,
+                                                              float* __restrict__ vertex, float* __restrict__ normal,
+                                                              uint8_t* __restrict__ rgb, u64* __restrict__ counters) {
+    const int view = blockIdx.x / bpv;
+    const int tile = (blockIdx.x - view * bpv) * CLOUD_WAVES + (threadIdx.x >> 6);
+    if (tile >= tiles) return;                                   // the whole wave
+    const int lane = bf_lane();
+    const int u = (tile % tiles_x) * 8 + (lane & 7), v = (tile / tiles_x) * 8 + (lane >> 3);
+    const bool in_image = u < W && v < H;
+    const float* P = poses + 16 * view;
+    bool finite = true;
+    for (int i = 0; i < 16; ++i) finite = finite && isfinite(P[i]);
+    const size_t pix = ((size_t)view * H + (in_image ? v : 0)) * W + (in_image ? u : 0);
+    float out_d = 0.f, vx = 0.f, vy = 0.f, vz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    unsigned cr = 0, cg = 0, cb = 0;
+    bool hit = false, behind = false, left = false, no_normal = false;
+    if (!finite) {
+        if (tile == 0 && lane == 0) atomicAdd(counters + RC_SKIPPED_POSE, 1ull);
+    } else if (in_image) {
+        const float a = ((float)u - cx) / fx, b = ((float)v - cy) / fy;
+        const float dx = P[0] * a + P[1] * b + P[2], dy = P[4] * a + P[5] * b + P[6], dz = P[8] * a + P[9] * b + P[10];
+        const float ox = P[3], oy = P[7], oz = P[11];
+        const float len = sqrtf(a * a + b * b + 1.0f);
+        const float trunc = (float)T * voxel, bs = 8.0f * voxel;
+        const float min_m = 0.25f * voxel;
+        u64 ckey = TSDF_EMPTY;
+        int cslot = -1;
+        float t = near_z, t0 = 0.f, s0 = 0.f;
+        bool have = false;                                       // (t0, s0) is a valid sample, the one before this
+        bool done = false;
+        for (int n = 0; n < max_steps && !done; ++n) {
+            if (!(t < far_z)) break;
+            const float px = ox + dx * t, py = oy + dy * t, pz = oz + dz * t;
+            const float bx = floorf(px / bs), by = floorf(py / bs), bz = floorf(pz / bs);
+            if (rc_block(keys, mask, bx, by, bz, ckey, cslot) < 0) {
+                float e = INFINITY;
+                if (dx != 0.f) e = fminf(e, ((dx > 0.f ? (bx + 1.0f) * bs : bx * bs) - px) / dx);
+                if (dy != 0.f) e = fminf(e, ((dy > 0.f ? (by + 1.0f) * bs : by * bs) - py) / dy);
+                if (dz != 0.f) e = fminf(e, ((dz > 0.f ? (bz + 1.0f) * bs : bz * bs) - pz) / dz);
+                t = t + (fmaxf(e, 0.f) + min_m / len);
+                have = false;
+                continue;
+            }
+            float s;
+            if (!rc_sample(keys, mask, vox, voxel, min_weight, px, py, pz, ckey, cslot, &s)) {
+                t = t + voxel / len;
+                have = false;
+                continue;
+            }
+            if (have && s0 >= 0.f && s < 0.f) {
+                const float th = t0 + (t - t0) * (s0 / (s0 - s));
+                out_d = th;
+                hit = done = true;
+                continue;
+            }
+            if (have && s0 < 0.f && s >= 0.f) {
+                behind = done = true;
+                continue;
+            }
+            t0 = t;
+            s0 = s;
+            have = true;
+            t = t + fmaxf(0.5f * fabsf(s) * trunc, min_m) / len;
+        }
+        left = !hit && !behind;
+        if (hit) {
+            vx = ox + dx * out_d;
+            vy = oy + dy * out_d;
+            vz = oz + dz * out_d;
+            const float h = 0.5f * voxel;
+            float xp, xm, yp, ym, zp, zm;
+            bool ok = rc_sample(keys, mask, vox, voxel, min_weight, vx + h, vy, vz, ckey, cslot, &xp);
+            ok = ok && rc_sample(keys, mask, vox, voxel, min_weight, vx - h, vy, vz, ckey, cslot, &xm);
+            ok = ok && rc_sample(keys, mask, vox, voxel, min_weight, vx, vy + h, vz, ckey, cslot, &yp);
+            ok = ok && rc_sample(keys, mask, vox, voxel, min_weight, vx, vy - h, vz, ckey, cslot, &ym);
+            ok = ok && rc_sample(keys, mask, vox, voxel, min_weight, vx, vy, vz + h, ckey, cslot, &zp);
+            ok = ok && rc_sample(keys, mask, vox, voxel, min_weight, vx, vy, vz - h, ckey, cslot, &zm);
+            float norm = 0.f;
+            if (ok) {
+                nx = xp - xm;
+                ny = yp - ym;
+                nz = zp - zm;
+                norm = sqrtf(nx * nx + ny * ny + nz * nz);
+            }
+            if (ok && norm > 0.f) {
+                nx = nx / norm;
+                ny = ny / norm;
+                nz = nz / norm;
+                if (rgb) {
+                    cr = cg = cb = 128u;
+                    const float qx = floorf(vx / voxel), qy = floorf(vy / voxel), qz = floorf(vz / voxel);
+                    const float lim = 8388600.0f;
+                    if (qx >= -lim && qx < lim && qy >= -lim && qy < lim && qz >= -lim && qz < lim) {
+                        const long long at = rc_voxel(keys, mask, (int)qx, (int)qy, (int)qz, ckey, cslot);
+                        if (at >= 0) {
+                            const int cw = vox[at + 2 * TSDF_VOX];
+                            if (cw > 0) {
+                                const unsigned hw = (unsigned)cw >> 1, c = (unsigned)cw;
+                                cr = ((unsigned)vox[at + 3 * TSDF_VOX] + hw) / c;
+                                cg = ((unsigned)vox[at + 4 * TSDF_VOX] + hw) / c;
+                                cb = ((unsigned)vox[at + 5 * TSDF_VOX] + hw) / c;
+                            }
+                        }
+                    }
+                }
+            } else {
+                hit = false;
+                no_normal = true;
+                out_d = vx = vy = vz = nx = ny = nz = 0.f;
+            }
+        }
+    }
+    rc_count(counters, RC_HITS, hit);
+    rc_count(counters, RC_BEHIND, behind);
+    rc_count(counters, RC_LEFT_RANGE, left);
+    rc_count(counters, RC_NO_NORMAL, no_normal);
+    if (!in_image) return;
+    depth[pix] = out_d;
+    vertex[pix * 3] = vx;
+    vertex[pix * 3 + 1] = vy;
+    vertex[pix * 3 + 2] = vz;
+    normal[pix * 3] = nx;
+    normal[pix * 3 + 1] = ny;
+    normal[pix * 3 + 2] = nz;
+    if (rgb) {
+        rgb[pix * 3] = (uint8_t)cr;
+        rgb[pix * 3 + 1] = (uint8_t)cg;
+        rgb[pix * 3 + 2] = (uint8_t)cb;
+    }
+}
+
+BF_API int bf_tsdf_raycast(const void* keys, const int32_t* vox, long long capacity, const float* poses, int V, int H, int W,
+                           float fx, float fy, float cx, float cy, float voxel, int trunc_voxels, float near_z, float far_z,
+                           int min_weight, int max_steps, float* depth, float* vertex, float* normal, uint8_t* rgb,
+                           void* counters, void* stream) {
+    if (!keys || !vox || !poses || !depth || !vertex || !normal || !counters || V <= 0 || H <= 0 || W <= 0 || capacity <= 0 ||
+        (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 || trunc_voxels > 64 || !(near_z >= 0.f) ||
+        !(far_z > near_z) || !(far_z < INFINITY) || min_weight < 1 || max_steps < 1 || !(fx > 0.f) || !(fy > 0.f))
+        return BF_ERR_ARG;
+    const long long tiles_x = (W + 7) / 8, tiles = tiles_x * ((H + 7) / 8);
+    const long long bpv = (tiles + CLOUD_WAVES - 1) / CLOUD_WAVES;
+    if (capacity >= (1ll << 31) || (long long)H * W * V >= (1ll << 31) / 3 || bpv * V >= (1ll << 31)) return BF_ERR_CAPACITY;
+    hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned)(bpv * V)), dim3(CLOUD_BLOCK), 0, bf_stream(stream), (const u64*)keys,
+                       (u64)(capacity - 1), (const int*)vox, poses, H, W, (int)tiles_x, (int)tiles, (int)bpv, fx, fy, cx, cy,
+                       voxel, trunc_voxels, near_z, far_z, min_weight, max_steps, depth, vertex, normal, rgb, (u64*)counters);
     return bf_check_launch();
 }

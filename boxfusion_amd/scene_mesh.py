@@ -109,6 +109,24 @@ class TsdfVolume:
         key, slot = self._blocks()
         return _lib.tsdf_surface(self.keys, self.vox, key, slot, self.voxel)
 
+    def raycast(self, poses, K, H, W, near=0.05, far=None, min_weight=1, colour=False):
+        """the volume seen from the camera-to-world poses [V,4,4] (or [4,4]) through the pinhole K at H x W
+        (bf_tsdf_raycast): depth f32 [V,H,W] (0: no hit), world vertex and normal f32 [V,H,W,3], rgb u8
+        [V,H,W,3] with colour=True else None, and counters int64 [8] (_lib.TSDF_RAYCAST_STATS), all on
+        the device.  far defaults to max_depth; a view with a non-finite pose is all zero and counted."""
+        poses = torch.as_tensor(np.asarray(poses, np.float32) if not torch.is_tensor(poses) else poses)
+        poses = poses.to(self.device, torch.float32).reshape(-1, 4, 4)
+        K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float32).reshape(3, 3)
+        far = self.max_depth if far is None else float(far)
+        if not 0 <= near < far or int(min_weight) < 1:
+            raise ValueError("raycast: 0 <= near < far and min_weight >= 1")
+        # every step is at least a quarter voxel long: the range in quarter voxels bounds the march
+        steps = int(min(max(np.ceil((far - float(near)) / (0.25 * float(self.voxel))) + 16, 16), 1 << 20))
+        counters = torch.zeros(8, dtype=torch.int64, device=self.device)
+        d, v, n, c = _lib.tsdf_raycast(self.keys, self.vox, poses, (K[0, 0], K[1, 1], K[0, 2], K[1, 2]), H, W, self.voxel,
+                                       self.trunc_voxels, near, far, min_weight, steps, counters, colour=colour)
+        return d, v, n, c, counters
+
     def save_ply(self, path):
         from boxfusion_amd.visualize import mesh_to_ply
         v, c, f = self.mesh()

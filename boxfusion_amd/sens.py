@@ -8,7 +8,9 @@ of `DecodedFrameStream` for the exported tree of the same scene, the colour fram
 bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zlib on the host);
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
 the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
-scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume) and `... render
+scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume), `... track scene.sens
+POSES.npy [--recover-lost | --from-scratch]` poses from tracking the depth frames against that TSDF
+(tracking.track_sequence; for `SensFrameStream(poses=...)`) and `... render
 scene.sens OUT_DIR [--boxes SEQ_boxes.pkl] [--mesh]` orbit and top-down PNG views of the cloud, or with
 --mesh of the TSDF surface (no model needed).
 
@@ -173,11 +175,11 @@ class SensFrameStream:
     bf_zlib_decode_u16 (depth_decode="host": zlib.decompress); raw-ushort depth is uploaded as it
     is.  K defaults to the depth intrinsics (the colour image is resized to the depth size, as the
     reference's cv2.resize(color, (W, H)) does), depth_scale to the file's depth_shift; poses are
-    `poses_filled()`; frames start, start + step, ... below stop, `timestamp` = the frame's index
-    in the file."""
+    `poses_filled()` unless `poses` ([num_frames,4,4], e.g. from `sens track`) replaces them; frames
+    start, start + step, ... below stop, `timestamp` = the frame's index in the file."""
 
     def __init__(self, sens, K=None, depth_scale=None, device="cuda", video_id=0, batch=16, start=0, stop=None,
-                 step=1, color_decode="gpu", depth_decode="gpu"):
+                 step=1, color_decode="gpu", depth_decode="gpu", poses=None):
         self.sens = sens if isinstance(sens, SensFile) else SensFile(sens)
         s = self.sens
         if s.color_compression != 2:
@@ -195,7 +197,12 @@ class SensFrameStream:
         self.dev, self.video_id, self.batch = device, video_id, max(1, int(batch))
         self.frames = range(s.num_frames)[start:stop:step]
         self.color_decode, self.depth_decode = color_decode, depth_decode
-        self.poses = s.poses_filled()
+        if poses is None:
+            self.poses = s.poses_filled()
+        else:                                       # e.g. what `sens track --recover-lost` wrote
+            self.poses = np.asarray(poses, np.float32)
+            if self.poses.shape != (s.num_frames, 4, 4):
+                raise ValueError(f"poses: [{s.num_frames},4,4] (one per frame of the file), got {self.poses.shape}")
 
     def __len__(self):
         return len(self.frames)
@@ -323,6 +330,57 @@ def mesh(sens, voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth
     return vol
 
 
+def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth=10.0,
+          capacity=1 << 16, device="cuda", batch=16, **tracker_args):
+    """poses for the frames start, start + step, ... below stop by tracking.track_sequence: mode
+    "recover-lost" keeps the file's finite poses and tracks the frames written as -inf; "from-scratch"
+    starts at the first selected frame's pose (identity if it has none) and tracks every later frame.
+    The selected frames are decoded first and held on the device (2.1 MB per 480 x 640 frame): --step /
+    --stop bound that for a long capture.
+    Returns (poses f32 [num_frames,4,4]: the file's with the selected frames replaced, -inf where a
+    frame stayed lost; the frame indices; info per selected frame; the TsdfVolume)"""
+    import torch
+    from boxfusion_amd.scene_mesh import TsdfVolume
+    from boxfusion_amd.tracking import track_sequence
+    if mode not in ("recover-lost", "from-scratch"):
+        raise ValueError("mode: 'recover-lost' or 'from-scratch'")
+    stream = SensFrameStream(sens, device=device, batch=batch, start=start, stop=stop, step=step)
+    s = stream.sens
+    ids = list(stream.frames)
+    vol = TsdfVolume(voxel=voxel, trunc_voxels=trunc_voxels, capacity=capacity, max_depth=max_depth, device=device)
+    poses = s.poses.copy()
+    if not ids:
+        return poses, ids, [], vol
+    depths, colours, K = [], [], None
+    for sample in stream:
+        gt = sample["sensor_info"].gt
+        K = gt.depth.K[-1]
+        depths.append(sample["wide"]["depth"][-1])
+        colours.append(sample["wide"]["image"][-1].permute(1, 2, 0).contiguous())
+    first = s.poses[ids[0]] if np.isfinite(s.poses[ids[0]]).all() else np.eye(4, dtype=np.float32)
+    known = s.poses[ids] if mode == "recover-lost" else None
+    got, infos = track_sequence(torch.stack(depths), K, first_pose=first, known_poses=known, volume=vol,
+                                colours=torch.stack(colours), **tracker_args)
+    poses[ids] = got
+    return poses, ids, infos, vol
+
+
+def track_line(file_poses, poses, ids, infos):
+    """`sens track`'s summary: frames tracked / lost and, over the tracked frames for which the file has
+    a finite pose, the RMS translation difference after moving the first selected frame onto the
+    file's pose of it"""
+    tracked = [i for i, f in zip(ids, infos) if f.get("tracked") and not f["lost"]]
+    lost = [i for i, f in zip(ids, infos) if f["lost"]]
+    line = f"{len(ids)} frames: {len(tracked)} tracked, {len(lost)} lost"
+    both = [i for i in tracked if np.isfinite(file_poses[i]).all()]
+    if ids and both and np.isfinite(file_poses[ids[0]]).all() and np.isfinite(poses[ids[0]]).all():
+        align = file_poses[ids[0]].astype(np.float64) @ np.linalg.inv(poses[ids[0]].astype(np.float64))
+        d = [(align @ poses[i].astype(np.float64))[:3, 3] - file_poses[i][:3, 3].astype(np.float64) for i in both]
+        rms = float(np.sqrt(np.mean(np.sum(np.square(d), 1))))
+        line += f", rms translation difference to the file's poses {rms:.4f} m over {len(both)}"
+    return line
+
+
 def _cloud_arguments(p):
     p.add_argument("--voxel", type=float, default=0.02, help="voxel edge in metres")
     p.add_argument("--start", type=int, default=0)
@@ -353,6 +411,15 @@ def parser():
     pm.add_argument("out")
     from boxfusion_amd.scene_mesh import add_volume_arguments
     add_volume_arguments(pm)
+    pt = sub.add_parser("track", help="track the camera against a TSDF of the depth frames and write the poses as .npy")
+    pt.add_argument("sens")
+    pt.add_argument("poses", help="the output: float32 [num_frames,4,4], -inf where a frame stayed lost")
+    mode = pt.add_mutually_exclusive_group()
+    mode.add_argument("--recover-lost", action="store_true",
+                      help="keep the file's finite poses and track the frames it wrote as -inf (the default)")
+    mode.add_argument("--from-scratch", action="store_true", help="ignore the file's poses after the first frame's")
+    pt.add_argument("--mesh", help="also write the fused surface as a PLY")
+    add_volume_arguments(pt)
     pr = sub.add_parser("render", help="write orbit and top-down PNG views of the scene's point cloud (and boxes)")
     pr.add_argument("sens")
     pr.add_argument("out", help="the directory of overview_<k>.png and overview_top.png")
@@ -381,7 +448,7 @@ def main(argv=None):
         if a.mesh:
             from boxfusion_amd.scene_mesh import check_volume_arguments
             check_volume_arguments(p, a)
-    if a.cmd == "mesh":
+    if a.cmd in ("mesh", "track"):
         from boxfusion_amd.scene_mesh import check_volume_arguments
         check_volume_arguments(p, a)
         if not os.path.isfile(a.sens):
@@ -399,6 +466,15 @@ def main(argv=None):
             nv, nf = vol.save_ply(a.out)
             print(f"{nv} vertices, {nf} faces -> {a.out}")
             print(vol.stats_line())
+        elif a.cmd == "track":
+            mode = "from-scratch" if a.from_scratch else "recover-lost"
+            poses, ids, infos, vol = track(s, mode, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth,
+                                           a.capacity)
+            np.save(a.poses, poses)
+            print(track_line(s.poses, poses, ids, infos) + f" -> {a.poses}")
+            if a.mesh:
+                nv, nf = vol.save_ply(a.mesh)
+                print(f"{nv} vertices, {nf} faces -> {a.mesh}")
         elif a.cmd == "render" and a.mesh:
             vol = mesh(s, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth, a.capacity)
             paths = render.write_overviews(None, render.load_boxes_argument(a.boxes), a.out, views=a.views, size=a.size,

@@ -1,0 +1,157 @@
+"""Camera tracking against the scene's TSDF: the KinectFusion loop over a `scene_mesh.TsdfVolume`.
+
+`TsdfVolume.raycast` reads the fused model back as a predicted vertex / normal map from a pose
+(bf_tsdf_raycast); `IcpTracker.track` aligns a new depth frame to that prediction by projective
+point-to-plane ICP: per iteration one bf_icp_reduce (the 6-DoF normal equations, summed on the
+device in a fixed order), one read-back of 32 doubles, a 6 x 6 solve on the host and T <- exp(xi) T.
+`track_sequence` alternates tracking and integration over a run of depth frames, either for every
+frame (a recording without poses) or only for the frames whose pose is not finite (a capture that
+lost tracking: ScanNet writes -inf there and `SensFile.poses_filled()` repeats the last valid pose).
+
+A frame the tracker cannot place is *lost*: its pose is all -inf, the capture format's own
+convention, which `TsdfVolume.integrate`, the renderer and the GT filter already skip.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from boxfusion_amd import _lib
+
+LOST = np.full((4, 4), -np.inf, np.float32)
+
+
+def se3_exp(xi):
+    """the closed-form SE(3) exponential of xi = (omega, t) -> f64 [4,4]"""
+    w, t = np.asarray(xi[:3], np.float64), np.asarray(xi[3:], np.float64)
+    th = float(np.sqrt(w @ w))
+    Wx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-9:
+        A, B, C = 1.0 - th * th / 6, 0.5 - th * th / 24, 1.0 / 6 - th * th / 120
+    else:
+        A, B, C = np.sin(th) / th, (1 - np.cos(th)) / (th * th), (th - np.sin(th)) / (th ** 3)
+    out = np.eye(4)
+    out[:3, :3] = np.eye(3) + A * Wx + B * (Wx @ Wx)
+    out[:3, 3] = (np.eye(3) + B * Wx + C * (Wx @ Wx)) @ t
+    return out
+
+
+def world_to_camera(pose):
+    """rows f64 [3,4] of the inverse of a rigid camera-to-world pose"""
+    P = np.asarray(pose, np.float64).reshape(4, 4)
+    Rt = P[:3, :3].T
+    return np.concatenate([Rt, -(Rt @ P[:3, 3])[:, None]], 1)
+
+
+def normal_matrix(out):
+    """J^T J f64 [6,6] from bf_icp_reduce's 21 upper-triangle entries"""
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = out[:21]
+    return A + np.triu(A, 1).T
+
+
+class IcpTracker:
+    """projective point-to-plane ICP of depth frames (H x W, pinhole K) against `volume`.
+
+    strides / iters: the coarse-to-fine schedule (pixels (stride i, stride j) of the live frame; the
+    stride stands in for a depth pyramid).  dist_max (default 4 truncation distances) and cos_min gate
+    a correspondence by its distance and by the angle between the normals; jump (default one truncation
+    distance) is the depth step across which no live normal is formed.  A frame is lost when fewer
+    than min_inlier_frac of the sampled pixels are inliers or J^T J's condition number exceeds
+    cond_max (a single plane leaves three directions unobserved: rank 3)."""
+
+    def __init__(self, volume, K, H, W, strides=(4, 2, 1), iters=(4, 4, 4), dist_max=None, cos_min=0.8,
+                 min_inlier_frac=0.4, cond_max=1000.0, jump=None, near=0.05):
+        if len(strides) != len(iters) or not strides or min(strides) < 1 or min(iters) < 1:
+            raise ValueError("strides and iters: one positive iteration count per positive stride")
+        self.volume, self.H, self.W = volume, int(H), int(W)
+        self.K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float32).reshape(3, 3)
+        self.intr = (self.K[0, 0], self.K[1, 1], self.K[0, 2], self.K[1, 2])
+        trunc = float(volume.voxel) * volume.trunc_voxels
+        self.strides, self.iters = tuple(int(s) for s in strides), tuple(int(i) for i in iters)
+        self.dist_max = 4 * trunc if dist_max is None else float(dist_max)
+        self.jump = trunc if jump is None else float(jump)
+        self.cos_min, self.min_inlier_frac = float(cos_min), float(min_inlier_frac)
+        self.cond_max, self.near = float(cond_max), float(near)
+        self._out = torch.empty(32, dtype=torch.float64, device=volume.device)
+
+    def track(self, depth_m, pose_guess):
+        """depth_m f32 [H,W] metres (tensor or array) seen from about pose_guess [4,4] -> (pose f32 [4,4]
+        camera-to-world, or all -inf when the frame is lost; info: lost, iterations, inliers, sampled,
+        rms (metres, point to plane), cond)"""
+        vol = self.volume
+        depth_m = torch.as_tensor(depth_m).to(vol.device, torch.float32)
+        if tuple(depth_m.shape) != (self.H, self.W):
+            raise ValueError(f"track: depth [{self.H},{self.W}], got {tuple(depth_m.shape)}")
+        guess = np.asarray(pose_guess.cpu() if torch.is_tensor(pose_guess) else pose_guess, np.float32).reshape(4, 4)
+        info = dict(lost=True, iterations=0, inliers=0, sampled=0, rms=float("inf"), cond=float("inf"))
+        if not np.isfinite(guess).all():
+            return LOST.copy(), info
+        _, mv, mn, _, _ = vol.raycast(guess, self.K, self.H, self.W, near=self.near)
+        mv, mn = mv[0], mn[0]
+        lv, ln = _lib.depth_vertex_normal(depth_m, self.intr, vol.max_depth, self.jump)
+        T = guess.astype(np.float64)[:3].copy()
+        M = world_to_camera(guess)
+        for stride, n_it in zip(self.strides, self.iters):
+            sampled = -(-self.H // stride) * -(-self.W // stride)
+            for _ in range(n_it):
+                _lib.icp_reduce(lv, ln, stride, T, mv, mn, M, self.intr, self.dist_max, self.cos_min, out=self._out)
+                out = self._out.cpu().numpy()
+                info.update(iterations=info["iterations"] + 1, inliers=int(out[28]), sampled=sampled)
+                if out[28] < 6 or out[28] < self.min_inlier_frac * sampled:
+                    return LOST.copy(), info
+                A = normal_matrix(out)
+                ev = np.linalg.eigvalsh(A)
+                info["cond"] = float(ev[-1] / ev[0]) if ev[0] > 0 else float("inf")
+                info["rms"] = float(np.sqrt(out[27] / out[28]))
+                if not info["cond"] <= self.cond_max:
+                    return LOST.copy(), info
+                xi = np.linalg.solve(A, out[21:27])
+                T = (se3_exp(xi) @ np.concatenate([T, [[0.0, 0.0, 0.0, 1.0]]]))[:3]
+        pose = np.eye(4, dtype=np.float32)
+        pose[:3] = T.astype(np.float32)
+        info["lost"] = False
+        return pose, info
+
+
+def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, colours=None, **tracker_args):
+    """track and fuse a run of depth frames (depths f32 [N,H,W] metres, tensor or array) into `volume`
+    (a scene_mesh.TsdfVolume): frame 0 is integrated at its pose (known_poses[0], or without known_poses
+    first_pose, default identity); every later frame takes its known finite pose, or is tracked from
+    the last good pose, and is integrated unless it is lost.  known_poses [N,4,4] with -inf rows
+    recovers the lost frames of a capture; None tracks every frame.  colours u8 [N,Hc,Wc,3] colours
+    the volume.  Returns (poses f32 [N,4,4] with -inf for lost frames, info per frame; info['tracked']
+    says whether the pose came from the tracker)."""
+    if volume is None:
+        raise ValueError("track_sequence: volume=TsdfVolume(...) is required")
+    depths = torch.as_tensor(depths)
+    if depths.dim() != 3:
+        raise ValueError(f"track_sequence: depths [N,H,W], got {tuple(depths.shape)}")
+    depths = depths.to(volume.device, torch.float32)
+    N, H, W = depths.shape
+    if known_poses is not None:
+        known_poses = np.asarray(known_poses, np.float32).reshape(-1, 4, 4)
+        if len(known_poses) != N:
+            raise ValueError(f"track_sequence: {N} frames, {len(known_poses)} known poses")
+    tracker = IcpTracker(volume, K, H, W, **tracker_args)
+    poses = np.tile(LOST, (N, 1, 1))
+    infos, last = [], None
+    for i in range(N):
+        known = known_poses is not None and bool(np.isfinite(known_poses[i]).all())
+        if known:
+            pose, info = known_poses[i].copy(), dict(lost=False, tracked=False)
+        elif last is None and i == 0 and known_poses is None:
+            pose = np.eye(4, dtype=np.float32) if first_pose is None else np.asarray(first_pose, np.float32).reshape(4, 4)
+            info = dict(lost=False, tracked=False)
+        elif last is None:                                   # nothing fused yet: nothing to track against
+            pose, info = LOST.copy(), dict(lost=True, tracked=False)
+        else:
+            pose, info = tracker.track(depths[i], last)
+            info["tracked"] = True
+        infos.append(info)
+        poses[i] = pose
+        if info["lost"]:
+            continue
+        volume.integrate(depths[i], K, pose[None], None if colours is None else colours[i])
+        last = pose
+    return poses, infos

@@ -922,6 +922,55 @@ int bf_nn_min_dist2(const double* query, int Q, const double* points, long long 
 int bf_obb_iou_exact(const double* a, int P, const double* b, int G, double* iou, double* inter,
                      void* stream);
 
+/* ---- tracking: the volume read back from a pose, and a depth frame aligned to it ----------------
+ * bf_tsdf_raycast: V views (poses f32 [V,4,4] camera-to-world, one pinhole, H x W) of the volume
+ * (keys, vox, capacity as above; read-only).  One thread per pixel marches the ray o + R (a, b, 1) t,
+ * a = (u - cx) / fx, b = (v - cy) / fy, t the camera depth from near_z to far_z, in at most max_steps
+ * steps.  The field at a point is the trilinear interpolation (x, then y, then z) of sum q / w / 1024
+ * over the eight voxel centres around it, valid only when all eight have w >= min_weight (>= 1).
+ * Where the block under the point is absent the ray jumps to that block's exit face plus a quarter
+ * voxel; a valid sample s steps max(|s| trunc / 2, voxel / 4) metres, an invalid one a voxel.  s < 0
+ * is inside, s >= 0 outside; the first step from a valid outside sample to a valid inside one is the
+ * hit, placed by linear interpolation of the two values; a step from inside to outside ends the ray
+ * (the camera is behind that surface).  depth f32 [V,H,W] (0: no hit), vertex f32 [V,H,W,3] (world),
+ * normal f32 [V,H,W,3] (world; the normalised central differences of the field at the hit +- half a
+ * voxel, towards the outside; a hit with an invalid tap or a zero gradient is no hit), rgb u8
+ * [V,H,W,3] or NULL (the rounded mean colour of the voxel that holds the hit, 128 where it has none,
+ * 0 where there is no hit).  counters uint64 [8], added to: hits, rays ended behind a surface, rays
+ * that left the range or ran out of steps, views skipped for a non-finite pose (all zero), hits
+ * dropped for their normal, 0, 0, 0.  All f32, left to right, no contraction: the same bits as the
+ * numpy restatement in tests/track_ref.py. */
+int bf_tsdf_raycast(const void* keys, const int32_t* vox, long long capacity, const float* poses,
+                    int V, int H, int W, float fx, float fy, float cx, float cy, float voxel,
+                    int trunc_voxels, float near_z, float far_z, int min_weight, int max_steps,
+                    float* depth, float* vertex, float* normal, uint8_t* rgb, void* counters,
+                    void* stream);
+
+/* bf_depth_vertex_normal: depth f32 [H,W] metres -> camera-frame vertex f32 [H,W,3] = ((u - cx) d /
+ * fx, (v - cy) d / fy, d) and normal f32 [H,W,3] = (down - here) x (right - here) normalised, facing
+ * the camera.  Valid: 0 < d < max_depth.  The normal is 0 where the pixel, its right or its lower
+ * neighbour is invalid or differs from it by more than jump, and in the last row and column; an
+ * invalid pixel's vertex is 0. */
+int bf_depth_vertex_normal(const float* depth, int H, int W, float fx, float fy, float cx, float cy,
+                           float max_depth, float jump, float* vertex, float* normal, void* stream);
+
+/* bf_icp_reduce: the normal equations of one projective point-to-plane ICP iteration.  The live maps
+ * (f32 [H,W,3], camera frame) are sampled at pixels (stride i, stride j); T (host f64 [12], rows of
+ * [R | t], camera-to-world) is the estimate; the model maps (f32 [Hm,Wm,3], world) belong to the
+ * camera model_w2c (host f64 [12], world-to-camera) with the pinhole fx fy cx cy.  Per sample, in f64
+ * with + - * / only: p = T v; q = model_w2c p; the model pixel floor(fx qx / qz + cx + 0.5), floor(fy
+ * qy / qz + cy + 0.5); rejected when either normal is 0, qz <= 0, the pixel is off the image,
+ * |v_m - p|^2 > dist_max^2 or (R n) . n_m < cos_min; else r = n_m . (v_m - p), J = [p x n_m, n_m].
+ * out f64 [32]: the 21 upper-triangle entries of J^T J row by row, the 6 of J^T r, sum r^2, the
+ * inlier count, 0, 0, 0.  partials f64 [bf_icp_blocks(H, W, stride), 32] is workspace.  The order of
+ * the additions is fixed (a thread's four samples, a butterfly over the wave, the waves, the blocks
+ * the same way) and the grid depends on (H, W, stride) alone: the same bits on every run. */
+int bf_icp_blocks(int H, int W, int stride);
+int bf_icp_reduce(const float* live_vertex, const float* live_normal, int H, int W, int stride,
+                  const double* T, const float* model_vertex, const float* model_normal, int Hm,
+                  int Wm, const double* model_w2c, double fx, double fy, double cx, double cy,
+                  double dist_max, double cos_min, double* partials, double* out, void* stream);
+
 /* placement probe (diagnostic): n_wg workgroups on `stream`, each spinning `spin` cycles, write
  * out[2b] = HW_ID (CU bits 11:8, SH 12, SE 15:13) and out[2b+1] = XCC id -- which CUs a (CU-masked)
  * stream really runs on */

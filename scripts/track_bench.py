@@ -1,0 +1,141 @@
+"""Times of the tracking kernels at 480 x 640 (a measurement aid, no threshold):
+
+  raycast      bf_tsdf_raycast of one view of two volumes at 2 cm voxels: "wall", mesh_probe.py's smooth wall
+               fused from eight frames, seen from its first camera, and "room", a 4 x 3.5 x 2.6 m box room fused
+               from four frames looking into a corner, seen from the last of them; with the counters
+  live maps    bf_depth_vertex_normal of one frame
+  icp_reduce   one bf_icp_reduce (both kernels) of a room frame against the room's raycast, at strides 4 / 2 / 1
+  track        IcpTracker.track of the next room frame from the pose before it: wall-clock of the whole call, the
+               raycast, the twelve reductions, their read-backs and the host's 6 x 6 solves included
+
+Device times are the median of REPS runs between device events after a warm-up, with their min and max; the
+wall-clock is the median of REPS calls, each followed by a synchronisation.  --scale shrinks the image for a
+rehearsal.  One JSON line at the end."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from boxfusion_amd import _lib  # noqa: E402
+from boxfusion_amd.scene_mesh import TsdfVolume  # noqa: E402
+from boxfusion_amd.synthetic import SCANNET_K, Scene  # noqa: E402
+from boxfusion_amd.tracking import IcpTracker, world_to_camera  # noqa: E402
+
+REPS = 9
+LO, HI = np.array([-2.0, -1.7, -1.3]), np.array([2.0, 1.8, 1.3])
+
+
+def device_ms(fn):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(REPS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b))
+    return dict(ms=round(float(np.median(out)), 4), min=round(float(min(out)), 4), max=round(float(max(out)), 4))
+
+
+def look_at(eye, target, up=(0.0, 0.0, 1.0)):
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, up)
+    right /= np.linalg.norm(right)
+    P = np.eye(4)
+    P[:3, 0], P[:3, 1], P[:3, 2], P[:3, 3] = right, np.cross(fwd, right), fwd, eye
+    return P.astype(np.float32)
+
+
+def room_depth(pose, K, H, W):
+    """the inside of the box LO .. HI from a camera in it: the nearest exit through the six slabs"""
+    P = pose.astype(np.float64)
+    v, u = np.mgrid[:H, :W].astype(np.float64)
+    a, b = (u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1]
+    best = np.full((H, W), np.inf)
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            d = P[i, 0] * a + P[i, 1] * b + P[i, 2]
+            t = np.where(d > 0, (HI[i] - P[i, 3]) / d, np.where(d < 0, (LO[i] - P[i, 3]) / d, np.inf))
+            best = np.minimum(best, np.where(t > 0, t, np.inf))
+    return best.astype(np.float32)
+
+
+def wall_depth(i, H, W):
+    v, u = np.mgrid[:H, :W].astype(np.float32)
+    u, v = u * (640.0 / W), v * (480.0 / H)
+    return (2.2 + 0.7 * np.sin(u / 210.0 + 0.3 * i) * np.cos(v / 170.0) + 0.001 * (u - 320)).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--scale", type=float, default=1.0, help="shrink the image by this factor (rehearsal)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("track_bench: needs a HIP device")
+    _lib.lib()
+    dev = torch.device("cuda")
+    H, W = max(int(480 * args.scale), 16), max(int(640 * args.scale), 16)
+    K = np.asarray(SCANNET_K, np.float32).reshape(3, 3).copy()
+    K[0] *= W / 640.0
+    K[1] *= H / 480.0
+    intr = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    out = dict(device=torch.cuda.get_device_name(0), hw=[H, W], reps=REPS)
+
+    scene = Scene(seed=0)
+    wall = TsdfVolume(voxel=0.02, trunc_voxels=4, capacity=1 << 16, device=dev)
+    wall_poses = np.stack([scene.pose(i) for i in range(8)]).astype(np.float32)
+    wall.integrate(torch.from_numpy(np.stack([wall_depth(i, H, W) for i in range(8)])).to(dev), K, wall_poses)
+
+    room = TsdfVolume(voxel=0.02, trunc_voxels=4, capacity=1 << 16, device=dev)
+    room_poses = [look_at([0.5 - 0.03 * i, 0.6 - 0.02 * i, 0.2 + 0.01 * i], [-2.0 + 0.05 * i, -1.7 + 0.03 * i, -1.3 + 0.03 * i])
+                  for i in range(5)]
+    room_depths = [torch.from_numpy(room_depth(p, K, H, W)).to(dev) for p in room_poses]
+    room.integrate(torch.stack(room_depths[:4]), K, np.stack(room_poses[:4]))
+    out["blocks"] = dict(wall=wall.stats()["blocks"], room=room.stats()["blocks"])
+
+    for name, vol, pose in (("wall", wall, wall_poses[0]), ("room", room, room_poses[3])):
+        row = device_ms(lambda: vol.raycast(pose, K, H, W))
+        row.update(zip(_lib.TSDF_RAYCAST_STATS, vol.raycast(pose, K, H, W)[4].cpu().tolist()))
+        out[f"raycast_{name}"] = row
+        print(f"raycast {name}", row, flush=True)
+
+    out["live_maps"] = device_ms(lambda: _lib.depth_vertex_normal(room_depths[4], intr, room.max_depth, 0.08))
+    print("live maps", out["live_maps"], flush=True)
+    lv, ln = _lib.depth_vertex_normal(room_depths[4], intr, room.max_depth, 0.08)
+    _, mv, mn, _, _ = room.raycast(room_poses[3], K, H, W)
+    T, M = room_poses[3].astype(np.float64)[:3], world_to_camera(room_poses[3])
+    for stride in (4, 2, 1):
+        row = device_ms(lambda: _lib.icp_reduce(lv, ln, stride, T, mv[0], mn[0], M, intr, 0.32, 0.8))
+        row.update(blocks=_lib.icp_blocks(H, W, stride),
+                   inliers=int(_lib.icp_reduce(lv, ln, stride, T, mv[0], mn[0], M, intr, 0.32, 0.8)[28].item()))
+        out[f"icp_reduce_stride{stride}"] = row
+        print(f"icp_reduce stride {stride}", row, flush=True)
+
+    tracker = IcpTracker(room, K, H, W)
+    pose, info = tracker.track(room_depths[4], room_poses[3])
+    torch.cuda.synchronize()
+    walls = []
+    for _ in range(REPS):
+        t = time.perf_counter()
+        tracker.track(room_depths[4], room_poses[3])
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t) * 1e3)
+    err = float(np.linalg.norm(pose[:3, 3] - room_poses[4][:3, 3])) if not info["lost"] else None
+    out["track"] = dict(wall_ms=round(float(np.median(walls)), 3), min=round(min(walls), 3), max=round(max(walls), 3),
+                        iterations=info["iterations"], lost=info["lost"], cond=round(info["cond"], 2),
+                        inlier_share=round(info["inliers"] / max(info["sampled"], 1), 3), translation_error_m=err)
+    print("track", out["track"], flush=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
