@@ -1510,6 +1510,76 @@ def icp_reduce(live_vertex, live_normal, stride, T, model_vertex, model_normal, 
     return out
 
 
+def _grey_u8_work(rgb, out=None):
+    return dict(kind="grey_u8", n=int(rgb.numel() // 3)), 0.0, float(rgb.numel()) * 7 / 3
+
+
+@_timed(_grey_u8_work)
+def grey_u8(rgb, out=None):
+    """RGB images u8 [H,W,3] or [B,H,W,3] -> intensity f32 [H,W] or [B,H,W] = ((77 R + 150 G + 29 B + 128)
+    >> 8) / 255 (bf_grey_u8)"""
+    _need(rgb, torch.uint8, "grey_u8: rgb")
+    x = rgb[None] if rgb.dim() == 3 else rgb
+    if x.dim() != 4 or x.shape[-1] != 3:
+        raise HipError(f"grey_u8: RGB images [B,H,W,3], got {tuple(rgb.shape)}")
+    x = x.contiguous()
+    B, H, W, _ = x.shape
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.numel() != B * H * W or not out.is_contiguous():
+        raise HipError("grey_u8: out f32 [B,H,W]")
+    _check(lib().bf_grey_u8(_ptr(x), c_int(B), c_int(H), c_int(W), _ptr(out), _stream()), "bf_grey_u8")
+    out = out.view(B, H, W)
+    return out[0] if rgb.dim() == 3 else out
+
+
+def _photo_reduce_work(live_vertex, live_intensity, stride, T, ref_intensity, ref_depth, ref_w2c, intr, dist_max,
+                       intensity_max, out=None):
+    n = float(live_vertex.shape[0] // stride) * (live_vertex.shape[1] // stride)
+    return dict(kind="photo_reduce", n=int(n), stride=int(stride)), n * 130.0, n * 36.0
+
+
+@_timed(_photo_reduce_work)
+def photo_reduce(live_vertex, live_intensity, stride, T, ref_intensity, ref_depth, ref_w2c, intr, dist_max, intensity_max,
+                 out=None):
+    """the normal equations of the photometric term (bf_photo_reduce): out f64 [32] on the device in
+    icp_reduce's layout.  live_vertex f32 [H,W,3] (camera frame) and live_intensity f32 [H,W] of the new
+    frame, T host f64 [3,4] camera-to-world; ref_intensity and ref_depth f32 [Hr,Wr] of the last placed
+    frame, whose camera is ref_w2c (host f64 [3,4]) with the pinhole intr"""
+    _need(live_vertex, torch.float32, "photo_reduce: live_vertex")
+    if live_vertex.dim() != 3 or live_vertex.shape[2] != 3:
+        raise HipError(f"photo_reduce: live_vertex [H,W,3], got {tuple(live_vertex.shape)}")
+    for t, name in ((live_intensity, "live_intensity"), (ref_intensity, "ref_intensity"), (ref_depth, "ref_depth")):
+        _need(t, torch.float32, f"photo_reduce: {name}")
+        if t.dim() != 2:
+            raise HipError(f"photo_reduce: {name} [H,W], got {tuple(t.shape)}")
+    if live_intensity.shape != live_vertex.shape[:2] or ref_intensity.shape != ref_depth.shape:
+        raise HipError("photo_reduce: an intensity map of the vertex map's size, and of the reference depth's")
+    stride = int(stride)
+    if stride < 1:
+        raise HipError("photo_reduce: stride >= 1")
+    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    M = np.ascontiguousarray(np.asarray(ref_w2c, np.float64).reshape(-1)[:12])
+    if T.size != 12 or M.size != 12:
+        raise HipError("photo_reduce: T and ref_w2c f64 [3,4]")
+    H, W = live_vertex.shape[:2]
+    Hr, Wr = ref_intensity.shape
+    dev = live_vertex.device
+    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(32, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != 32:
+        raise HipError("photo_reduce: out f64 [32]")
+    dp = ctypes.POINTER(c_double)
+    fx, fy, cx, cy = (c_double(float(np.float32(v))) for v in intr)
+    _check(lib().bf_photo_reduce(_ptr(live_vertex.contiguous()), _ptr(live_intensity.contiguous()), c_int(H), c_int(W),
+                                 c_int(stride), T.ctypes.data_as(dp), _ptr(ref_intensity.contiguous()),
+                                 _ptr(ref_depth.contiguous()), c_int(Hr), c_int(Wr), M.ctypes.data_as(dp), fx, fy, cx, cy,
+                                 c_double(float(dist_max)), c_double(float(intensity_max)), _ptr(partials), _ptr(out),
+                                 _stream()), "bf_photo_reduce")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # headless renderer (bf_render.hip)
 # ------------------------------------------------------------------------------------------

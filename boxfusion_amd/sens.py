@@ -9,7 +9,7 @@ bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zl
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
 the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
 scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume), `... track scene.sens
-POSES.npy [--recover-lost | --from-scratch]` poses from tracking the depth frames against that TSDF
+POSES.npy [--recover-lost | --from-scratch] [--photometric]` poses from tracking the depth frames against that TSDF
 (tracking.track_sequence; for `SensFrameStream(poses=...)`) and `... render
 scene.sens OUT_DIR [--boxes SEQ_boxes.pkl] [--mesh]` orbit and top-down PNG views of the cloud, or with
 --mesh of the TSDF surface (no model needed).
@@ -331,10 +331,12 @@ def mesh(sens, voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth
 
 
 def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth=10.0,
-          capacity=1 << 16, device="cuda", batch=16, **tracker_args):
+          capacity=1 << 16, device="cuda", batch=16, photometric=False, **tracker_args):
     """poses for the frames start, start + step, ... below stop by tracking.track_sequence: mode
     "recover-lost" keeps the file's finite poses and tracks the frames written as -inf; "from-scratch"
     starts at the first selected frame's pose (identity if it has none) and tracks every later frame.
+    photometric=True adds the colour frames' intensity residual to the depth ICP, which places views
+    that a single plane fills.
     The selected frames are decoded first and held on the device (2.1 MB per 480 x 640 frame): --step /
     --stop bound that for a long capture.
     Returns (poses f32 [num_frames,4,4]: the file's with the selected frames replaced, -inf where a
@@ -360,7 +362,7 @@ def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=N
     first = s.poses[ids[0]] if np.isfinite(s.poses[ids[0]]).all() else np.eye(4, dtype=np.float32)
     known = s.poses[ids] if mode == "recover-lost" else None
     got, infos = track_sequence(torch.stack(depths), K, first_pose=first, known_poses=known, volume=vol,
-                                colours=torch.stack(colours), **tracker_args)
+                                colours=torch.stack(colours), photometric=photometric, **tracker_args)
     poses[ids] = got
     return poses, ids, infos, vol
 
@@ -419,6 +421,9 @@ def parser():
                       help="keep the file's finite poses and track the frames it wrote as -inf (the default)")
     mode.add_argument("--from-scratch", action="store_true", help="ignore the file's poses after the first frame's")
     pt.add_argument("--mesh", help="also write the fused surface as a PLY")
+    pt.add_argument("--photometric", action="store_true",
+                    help="track with the colour frames too (an intensity residual against the last placed frame): "
+                         "places a textured wall, floor or table top that fills the view")
     add_volume_arguments(pt)
     pr = sub.add_parser("render", help="write orbit and top-down PNG views of the scene's point cloud (and boxes)")
     pr.add_argument("sens")
@@ -469,7 +474,7 @@ def main(argv=None):
         elif a.cmd == "track":
             mode = "from-scratch" if a.from_scratch else "recover-lost"
             poses, ids, infos, vol = track(s, mode, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth,
-                                           a.capacity)
+                                           a.capacity, photometric=a.photometric)
             np.save(a.poses, poses)
             print(track_line(s.poses, poses, ids, infos) + f" -> {a.poses}")
             if a.mesh:

@@ -4,6 +4,10 @@
 (bf_tsdf_raycast); `IcpTracker.track` aligns a new depth frame to that prediction by projective
 point-to-plane ICP: per iteration one bf_icp_reduce (the 6-DoF normal equations, summed on the
 device in a fixed order), one read-back of 32 doubles, a 6 x 6 solve on the host and T <- exp(xi) T.
+With a colour image beside the depth frame, `track(depth, guess, rgb)` adds a photometric term: the
+new frame's intensities against the last placed frame's image (bf_photo_reduce, the same 32 doubles),
+A = A_geo + w^2 A_photo.  A texture fixes the directions a plane leaves free, so a wall, a floor or a
+table top that fills the view can be placed.
 `track_sequence` alternates tracking and integration over a run of depth frames, either for every
 frame (a recording without poses) or only for the frames whose pose is not finite (a capture that
 lost tracking: ScanNet writes -inf there and `SensFile.poses_filled()` repeats the last valid pose).
@@ -58,10 +62,17 @@ class IcpTracker:
     a correspondence by its distance and by the angle between the normals; jump (default one truncation
     distance) is the depth step across which no live normal is formed.  A frame is lost when fewer
     than min_inlier_frac of the sampled pixels are inliers or J^T J's condition number exceeds
-    cond_max (a single plane leaves three directions unobserved: rank 3)."""
+    cond_max (a single plane leaves three directions unobserved: rank 3).
+
+    photo_weight / intensity_max: the photometric term of `track(depth, guess, rgb)`.  Its normal
+    equations enter with photo_weight squared (intensities are 0 .. 1, the geometric residual is in
+    metres); a sample whose intensity differs from the reference by more than intensity_max is left
+    out, and so is one whose depth differs from the reference frame's by more than dist_max.  The
+    inlier share is still judged on the geometric count, the condition number on the combined matrix:
+    an untextured plane adds exactly nothing and stays lost."""
 
     def __init__(self, volume, K, H, W, strides=(4, 2, 1), iters=(4, 4, 4), dist_max=None, cos_min=0.8,
-                 min_inlier_frac=0.4, cond_max=1000.0, jump=None, near=0.05):
+                 min_inlier_frac=0.4, cond_max=1000.0, jump=None, near=0.05, photo_weight=1.0, intensity_max=0.3):
         if len(strides) != len(iters) or not strides or min(strides) < 1 or min(iters) < 1:
             raise ValueError("strides and iters: one positive iteration count per positive stride")
         self.volume, self.H, self.W = volume, int(H), int(W)
@@ -73,20 +84,58 @@ class IcpTracker:
         self.jump = trunc if jump is None else float(jump)
         self.cos_min, self.min_inlier_frac = float(cos_min), float(min_inlier_frac)
         self.cond_max, self.near = float(cond_max), float(near)
+        self.photo_weight, self.intensity_max = float(photo_weight), float(intensity_max)
+        if not self.photo_weight >= 0 or not self.intensity_max >= 0:
+            raise ValueError("photo_weight and intensity_max: not negative")
         self._out = torch.empty(32, dtype=torch.float64, device=volume.device)
+        self._both = torch.empty((2, 32), dtype=torch.float64, device=volume.device)
+        self._ref = None                                     # (intensity f32 [H,W], depth f32 [H,W], world -> camera)
 
-    def track(self, depth_m, pose_guess):
+    def _depth(self, depth_m, who):
+        depth_m = torch.as_tensor(depth_m).to(self.volume.device, torch.float32)
+        if tuple(depth_m.shape) != (self.H, self.W):
+            raise ValueError(f"{who}: depth [{self.H},{self.W}], got {tuple(depth_m.shape)}")
+        return depth_m
+
+    def _grey(self, rgb, who):
+        """rgb u8 [Hc,Wc,3] (tensor or array) -> intensity f32 [H,W], resized first as TsdfVolume.integrate does"""
+        rgb = torch.as_tensor(rgb).to(self.volume.device)
+        if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"{who}: rgb u8 [Hc,Wc,3], got {rgb.dtype} {tuple(rgb.shape)}")
+        if tuple(rgb.shape[:2]) != (self.H, self.W):
+            rgb = _lib.resize_bicubic_u8(rgb, self.H, self.W)
+        return _lib.grey_u8(rgb)
+
+    def set_reference(self, rgb, depth_m, pose):
+        """the frame the photometric term compares with: rgb u8 [Hc,Wc,3] and depth_m f32 [H,W] of a frame
+        whose camera-to-world pose [4,4] is known.  A pose with a non-finite entry clears the reference."""
+        pose = np.asarray(pose.cpu() if torch.is_tensor(pose) else pose, np.float32).reshape(4, 4)
+        if not np.isfinite(pose).all():
+            self._ref = None
+            return
+        self._ref = (self._grey(rgb, "set_reference"), self._depth(depth_m, "set_reference").contiguous(),
+                     world_to_camera(pose))
+
+    def track(self, depth_m, pose_guess, rgb=None):
         """depth_m f32 [H,W] metres (tensor or array) seen from about pose_guess [4,4] -> (pose f32 [4,4]
         camera-to-world, or all -inf when the frame is lost; info: lost, iterations, inliers, sampled,
-        rms (metres, point to plane), cond)"""
+        rms (metres, point to plane), cond).  With rgb u8 [Hc,Wc,3] and a reference (set_reference, or
+        the last frame this call placed with an image) the photometric term joins in: both reductions
+        per iteration, one read-back of the two rows, and info gains photo_inliers and photo_rms
+        (intensity, 0 .. 1).  A frame placed with rgb becomes the reference; a lost one never does."""
         vol = self.volume
-        depth_m = torch.as_tensor(depth_m).to(vol.device, torch.float32)
-        if tuple(depth_m.shape) != (self.H, self.W):
-            raise ValueError(f"track: depth [{self.H},{self.W}], got {tuple(depth_m.shape)}")
+        depth_m = self._depth(depth_m, "track")
         guess = np.asarray(pose_guess.cpu() if torch.is_tensor(pose_guess) else pose_guess, np.float32).reshape(4, 4)
         info = dict(lost=True, iterations=0, inliers=0, sampled=0, rms=float("inf"), cond=float("inf"))
+        photo = rgb is not None and self._ref is not None
+        if photo:
+            info.update(photo_inliers=0, photo_rms=float("inf"))
         if not np.isfinite(guess).all():
             return LOST.copy(), info
+        if photo:
+            live = self._grey(rgb, "track")
+            ri, rd, Mr = self._ref
+            lam2 = np.float64(self.photo_weight) * np.float64(self.photo_weight)
         _, mv, mn, _, _ = vol.raycast(guess, self.K, self.H, self.W, near=self.near)
         mv, mn = mv[0], mn[0]
         lv, ln = _lib.depth_vertex_normal(depth_m, self.intr, vol.max_depth, self.jump)
@@ -95,33 +144,48 @@ class IcpTracker:
         for stride, n_it in zip(self.strides, self.iters):
             sampled = -(-self.H // stride) * -(-self.W // stride)
             for _ in range(n_it):
-                _lib.icp_reduce(lv, ln, stride, T, mv, mn, M, self.intr, self.dist_max, self.cos_min, out=self._out)
-                out = self._out.cpu().numpy()
+                if photo:
+                    _lib.icp_reduce(lv, ln, stride, T, mv, mn, M, self.intr, self.dist_max, self.cos_min, out=self._both[0])
+                    _lib.photo_reduce(lv, live, stride, T, ri, rd, Mr, self.intr, self.dist_max, self.intensity_max,
+                                      out=self._both[1])
+                    out, po = self._both.cpu().numpy()
+                    info.update(photo_inliers=int(po[28]),
+                                photo_rms=float(np.sqrt(po[27] / po[28])) if po[28] > 0 else float("inf"))
+                else:
+                    _lib.icp_reduce(lv, ln, stride, T, mv, mn, M, self.intr, self.dist_max, self.cos_min, out=self._out)
+                    out = self._out.cpu().numpy()
                 info.update(iterations=info["iterations"] + 1, inliers=int(out[28]), sampled=sampled)
                 if out[28] < 6 or out[28] < self.min_inlier_frac * sampled:
                     return LOST.copy(), info
-                A = normal_matrix(out)
+                A, b = normal_matrix(out), out[21:27]
+                if photo:
+                    A, b = A + lam2 * normal_matrix(po), b + lam2 * po[21:27]
                 ev = np.linalg.eigvalsh(A)
                 info["cond"] = float(ev[-1] / ev[0]) if ev[0] > 0 else float("inf")
                 info["rms"] = float(np.sqrt(out[27] / out[28]))
                 if not info["cond"] <= self.cond_max:
                     return LOST.copy(), info
-                xi = np.linalg.solve(A, out[21:27])
+                xi = np.linalg.solve(A, b)
                 T = (se3_exp(xi) @ np.concatenate([T, [[0.0, 0.0, 0.0, 1.0]]]))[:3]
         pose = np.eye(4, dtype=np.float32)
         pose[:3] = T.astype(np.float32)
         info["lost"] = False
+        if rgb is not None:
+            self._ref = (live if photo else self._grey(rgb, "track"), depth_m.contiguous(), world_to_camera(pose))
         return pose, info
 
 
-def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, colours=None, **tracker_args):
+def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, colours=None, photometric=False,
+                   **tracker_args):
     """track and fuse a run of depth frames (depths f32 [N,H,W] metres, tensor or array) into `volume`
     (a scene_mesh.TsdfVolume): frame 0 is integrated at its pose (known_poses[0], or without known_poses
     first_pose, default identity); every later frame takes its known finite pose, or is tracked from
     the last good pose, and is integrated unless it is lost.  known_poses [N,4,4] with -inf rows
     recovers the lost frames of a capture; None tracks every frame.  colours u8 [N,Hc,Wc,3] colours
-    the volume.  Returns (poses f32 [N,4,4] with -inf for lost frames, info per frame; info['tracked']
-    says whether the pose came from the tracker)."""
+    the volume; photometric=True (which needs colours) also hands each tracked frame's image to the
+    tracker, with the last frame that has a pose as the photometric reference.  Returns (poses f32
+    [N,4,4] with -inf for lost frames, info per frame; info['tracked'] says whether the pose came from
+    the tracker)."""
     if volume is None:
         raise ValueError("track_sequence: volume=TsdfVolume(...) is required")
     depths = torch.as_tensor(depths)
@@ -133,6 +197,8 @@ def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, co
         known_poses = np.asarray(known_poses, np.float32).reshape(-1, 4, 4)
         if len(known_poses) != N:
             raise ValueError(f"track_sequence: {N} frames, {len(known_poses)} known poses")
+    if photometric and colours is None:
+        raise ValueError("track_sequence: photometric=True needs colours")
     tracker = IcpTracker(volume, K, H, W, **tracker_args)
     poses = np.tile(LOST, (N, 1, 1))
     infos, last = [], None
@@ -146,12 +212,14 @@ def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, co
         elif last is None:                                   # nothing fused yet: nothing to track against
             pose, info = LOST.copy(), dict(lost=True, tracked=False)
         else:
-            pose, info = tracker.track(depths[i], last)
+            pose, info = tracker.track(depths[i], last, colours[i]) if photometric else tracker.track(depths[i], last)
             info["tracked"] = True
         infos.append(info)
         poses[i] = pose
         if info["lost"]:
             continue
         volume.integrate(depths[i], K, pose[None], None if colours is None else colours[i])
+        if photometric and not info.get("tracked"):
+            tracker.set_reference(colours[i], depths[i], pose)
         last = pose
     return poses, infos

@@ -971,6 +971,29 @@ int bf_icp_reduce(const float* live_vertex, const float* live_normal, int H, int
                   int Wm, const double* model_w2c, double fx, double fy, double cx, double cy,
                   double dist_max, double cos_min, double* partials, double* out, void* stream);
 
+/* bf_grey_u8: rgb u8 [B,H,W,3] -> intensity f32 [B,H,W] = (float)((77 R + 150 G + 29 B + 128) >> 8) /
+ * 255.0f. */
+int bf_grey_u8(const uint8_t* rgb, int B, int H, int W, float* out, void* stream);
+
+/* bf_photo_reduce: the normal equations of the tracker's photometric term, bf_icp_reduce's companion:
+ * the same sampling of the live frame (its vertex map f32 [H,W,3] and its intensity f32 [H,W]), the
+ * same order of additions, the same layout of partials and out.  The reference is the last placed
+ * frame: its intensity and its sensor depth (f32 [Hr,Wr]) and its camera ref_w2c (host f64 [12]) with
+ * the pinhole fx fy cx cy.  Per sample, in f64 with + - * /, floor and comparisons only: p = T v;
+ * q = ref_w2c p; u = fx qx / qz + cx, w = fy qy / qz + cy; rejected when v.z <= 0, qz <= 0, floor(u)
+ * is outside 0 .. Wr - 2 or floor(w) outside 0 .. Hr - 2 (no reference load before this), the
+ * reference depth D at (floor(w + 0.5), floor(u + 0.5)) is not > 0 or |D - qz| > dist_max, or
+ * |r| > intensity_max; c is the bilinear intensity at (u, w), (gx, gy) the derivative of that
+ * interpolant, r = I_live - c, h = (gx fx / qz, gy fy / qz, -(gx fx qx + gy fy qy) / qz^2),
+ * g = R^T h with R the left 3 x 3 of ref_w2c, J = [p x g, g].  out f64 [32]: the 21 upper-triangle
+ * entries of J^T J, the 6 of J^T r, sum r^2, the inlier count, 0, 0, 0.  partials f64
+ * [bf_icp_blocks(H, W, stride), 32] is workspace. */
+int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H, int W, int stride,
+                    const double* T, const float* ref_intensity, const float* ref_depth, int Hr,
+                    int Wr, const double* ref_w2c, double fx, double fy, double cx, double cy,
+                    double dist_max, double intensity_max, double* partials, double* out,
+                    void* stream);
+
 /* placement probe (diagnostic): n_wg workgroups on `stream`, each spinning `spin` cycles, write
  * out[2b] = HW_ID (CU bits 11:8, SH 12, SE 15:13) and out[2b+1] = XCC id -- which CUs a (CU-masked)
  * stream really runs on */

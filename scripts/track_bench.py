@@ -5,8 +5,12 @@
                from four frames looking into a corner, seen from the last of them; with the counters
   live maps    bf_depth_vertex_normal of one frame
   icp_reduce   one bf_icp_reduce (both kernels) of a room frame against the room's raycast, at strides 4 / 2 / 1
+  grey         bf_grey_u8 of one colour frame
+  photo_reduce one bf_photo_reduce (both kernels) of that room frame against the frame before it, textured, at
+               strides 4 / 2 / 1
   track        IcpTracker.track of the next room frame from the pose before it: wall-clock of the whole call, the
                raycast, the twelve reductions, their read-backs and the host's 6 x 6 solves included
+  track_rgb    the same call with the frame's image: bf_grey_u8 and twelve bf_photo_reduce more, one read-back each
 
 Device times are the median of REPS runs between device events after a warm-up, with their min and max; the
 wall-clock is the median of REPS calls, each followed by a synchronisation.  --scale shrinks the image for a
@@ -69,6 +73,18 @@ def room_depth(pose, K, H, W):
     return best.astype(np.float32)
 
 
+def room_image(pose, K, depth):
+    """u8 [H,W,3]: a smooth texture of the world point each pixel sees"""
+    P = pose.astype(np.float64)
+    H, W = depth.shape
+    v, u = np.mgrid[:H, :W].astype(np.float64)
+    d = depth.astype(np.float64)
+    a, b = (u - K[0, 2]) / K[0, 0] * d, (v - K[1, 2]) / K[1, 1] * d
+    x, y, z = [P[i, 0] * a + P[i, 1] * b + P[i, 2] * d + P[i, 3] for i in range(3)]
+    t = 0.5 + 0.16 * np.sin(5 * (x + z) + 1) + 0.14 * np.sin(6 * (y - z) - 0.5) + 0.10 * np.sin(3.5 * (x + y) + 2)
+    return np.repeat(np.rint(255.0 * t).astype(np.uint8)[..., None], 3, -1)
+
+
 def wall_depth(i, H, W):
     v, u = np.mgrid[:H, :W].astype(np.float32)
     u, v = u * (640.0 / W), v * (480.0 / H)
@@ -120,20 +136,36 @@ def main():
         out[f"icp_reduce_stride{stride}"] = row
         print(f"icp_reduce stride {stride}", row, flush=True)
 
+    rgbs = [torch.from_numpy(room_image(room_poses[i], K, room_depths[i].cpu().numpy())).to(dev) for i in (3, 4)]
+    out["grey"] = device_ms(lambda: _lib.grey_u8(rgbs[1]))
+    print("grey", out["grey"], flush=True)
+    ri, li, Mr = _lib.grey_u8(rgbs[0]), _lib.grey_u8(rgbs[1]), world_to_camera(room_poses[3])
+    for stride in (4, 2, 1):
+        row = device_ms(lambda: _lib.photo_reduce(lv, li, stride, T, ri, room_depths[3], Mr, intr, 0.32, 0.3))
+        row.update(blocks=_lib.icp_blocks(H, W, stride),
+                   inliers=int(_lib.photo_reduce(lv, li, stride, T, ri, room_depths[3], Mr, intr, 0.32, 0.3)[28].item()))
+        out[f"photo_reduce_stride{stride}"] = row
+        print(f"photo_reduce stride {stride}", row, flush=True)
+
     tracker = IcpTracker(room, K, H, W)
-    pose, info = tracker.track(room_depths[4], room_poses[3])
-    torch.cuda.synchronize()
-    walls = []
-    for _ in range(REPS):
-        t = time.perf_counter()
-        tracker.track(room_depths[4], room_poses[3])
-        torch.cuda.synchronize()
-        walls.append((time.perf_counter() - t) * 1e3)
-    err = float(np.linalg.norm(pose[:3, 3] - room_poses[4][:3, 3])) if not info["lost"] else None
-    out["track"] = dict(wall_ms=round(float(np.median(walls)), 3), min=round(min(walls), 3), max=round(max(walls), 3),
-                        iterations=info["iterations"], lost=info["lost"], cond=round(info["cond"], 2),
-                        inlier_share=round(info["inliers"] / max(info["sampled"], 1), 3), translation_error_m=err)
-    print("track", out["track"], flush=True)
+    for name, rgb in (("track", None), ("track_rgb", rgbs[1])):
+        walls = []
+        for _ in range(REPS + 1):                               # the first call is the warm-up
+            tracker.set_reference(rgbs[0], room_depths[3], room_poses[3])     # a frame placed with its image replaces it
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            pose, info = tracker.track(room_depths[4], room_poses[3], rgb)
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t) * 1e3)
+        walls = walls[1:]
+        err = float(np.linalg.norm(pose[:3, 3] - room_poses[4][:3, 3])) if not info["lost"] else None
+        out[name] = dict(wall_ms=round(float(np.median(walls)), 3), min=round(min(walls), 3), max=round(max(walls), 3),
+                         iterations=info["iterations"], lost=info["lost"], cond=round(info["cond"], 2),
+                         inlier_share=round(info["inliers"] / max(info["sampled"], 1), 3), translation_error_m=err)
+        if rgb is not None:
+            out[name].update(photo_inlier_share=round(info["photo_inliers"] / max(info["sampled"], 1), 3),
+                             photo_rms=round(info["photo_rms"], 5))
+        print(name, out[name], flush=True)
     print(json.dumps(out))
 
 
