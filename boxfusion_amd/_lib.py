@@ -1581,6 +1581,127 @@ def photo_reduce(live_vertex, live_intensity, stride, T, ref_intensity, ref_dept
 
 
 # ------------------------------------------------------------------------------------------
+# relocalisation (bf_fern.hip)
+# ------------------------------------------------------------------------------------------
+FERN_COUNTERS = ("observed", "added", "dropped_full")
+FERN_K_MAX = 8
+
+
+def fern_upload(table, cells, device):
+    """a host fern table i32 [F,5] (cell, tR, tG, tB, tD per fern; F a multiple of 8, every cell index
+    below `cells`) checked by bf_fern_table_check and copied to the device"""
+    t = np.ascontiguousarray(np.asarray(table, np.int32))
+    if t.ndim != 2 or t.shape[1] != 5:
+        raise HipError(f"fern_upload: table i32 [F,5], got {t.shape}")
+    _check(lib().bf_fern_table_check(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c_int(t.shape[0]), c_int(int(cells))),
+           "bf_fern_table_check")
+    return h2d(t, device)
+
+
+def _fern_frames(depth, rgb):
+    _need(depth, torch.float32, "fern_encode: depth")
+    d = depth[None] if depth.dim() == 2 else depth
+    if d.dim() != 3:
+        raise HipError(f"fern_encode: depth [H,W] or [B,H,W], got {tuple(depth.shape)}")
+    if rgb is not None:
+        _need(rgb, torch.uint8, "fern_encode: rgb")
+        rgb = rgb[None] if rgb.dim() == 3 else rgb
+        if tuple(rgb.shape) != tuple(d.shape) + (3,) or rgb.device != d.device:
+            raise HipError(f"fern_encode: rgb u8 {tuple(d.shape) + (3,)} beside the depth, got {tuple(rgb.shape)}")
+        rgb = rgb.contiguous()
+    return d.contiguous(), rgb
+
+
+def _fern_encode_work(depth, rgb, cell, max_depth, ferns, with_means=False, codes=None):
+    return dict(kind="fern_encode", n=int(depth.numel())), 0.0, float(depth.numel()) * (4 if rgb is None else 7)
+
+
+@_timed(_fern_encode_work)
+def fern_encode(depth, rgb, cell, max_depth, ferns, with_means=False, codes=None):
+    """frames (depth f32 [H,W] or [B,H,W] metres, rgb u8 of the same size with a last axis of 3, or None)
+    -> codes u32-in-int32 [B, F/8] under the device fern table `ferns` i32 [F,5] (bf_fern_encode); with
+    with_means=True (codes, means i32 [B, (H//cell) (W//cell), 4])"""
+    d, rgb = _fern_frames(depth, rgb)
+    _need(ferns, torch.int32, "fern_encode: ferns")
+    if ferns.dim() != 2 or ferns.shape[1] != 5 or ferns.device != d.device:
+        raise HipError(f"fern_encode: ferns i32 [F,5] on the depth's device, got {tuple(ferns.shape)}")
+    B, H, W = d.shape
+    F, cell = int(ferns.shape[0]), int(cell)
+    if codes is None:
+        codes = torch.empty((B, max(F // 8, 1)), dtype=torch.int32, device=d.device)
+    elif codes.dtype != torch.int32 or codes.numel() != B * (F // 8) or not codes.is_contiguous():
+        raise HipError("fern_encode: codes int32 [B, F/8]")
+    means = None
+    if with_means:
+        means = torch.empty((B, max(H // cell, 0) * max(W // cell, 0) if cell > 0 else 0, 4), dtype=torch.int32, device=d.device)
+    _check(lib().bf_fern_encode(_ptr(d), _ptr(rgb), c_int(B), c_int(H), c_int(W), c_int(cell), c_float(float(max_depth)),
+                                _ptr(ferns.contiguous()), c_int(F), _ptr(means), _ptr(codes), _stream()), "bf_fern_encode")
+    return (codes, means) if with_means else codes
+
+
+def _fern_search_work(table, n, n_upper, queries, k, with_rows=False, top=None):
+    return dict(kind="fern_search", n=int(n_upper), q=int(queries.shape[0])), 0.0, float(n_upper) * table.shape[1] * 4
+
+
+@_timed(_fern_search_work)
+def fern_search(table, n, n_upper, queries, k, with_rows=False, top=None):
+    """the k (<= 8) nearest keyframes of each query (bf_fern_search): table int32 [capacity, F/8] (the u32
+    codes), n int32 [1] on the device (the rows held), n_upper the host's bound of it, queries int32
+    [Q, F/8] -> top int32 [Q,k,2] of (distance, index), (-1, -1) beyond n; with_rows=True (top, rows
+    int32 [Q, n_upper] with -1 at and beyond n)"""
+    _need(table, torch.int32, "fern_search: table")
+    _need(queries, torch.int32, "fern_search: queries")
+    _need(n, torch.int32, "fern_search: n")
+    if table.dim() != 2 or queries.dim() != 2 or queries.shape[1] != table.shape[1] or n.numel() < 1:
+        raise HipError(f"fern_search: table [capacity, F/8], queries [Q, F/8], n [1]; got {tuple(table.shape)}, "
+                       f"{tuple(queries.shape)}, {tuple(n.shape)}")
+    if queries.device != table.device or n.device != table.device:
+        raise HipError("fern_search: table, n and queries on one device")
+    capacity, words = table.shape
+    Q, k, n_upper = int(queries.shape[0]), int(k), int(n_upper)
+    lib().bf_fern_search_blocks.restype = c_int
+    blocks = int(lib().bf_fern_search_blocks(c_int(n_upper)))
+    part = torch.empty((max(Q, 1), max(blocks, 1), max(k, 1)), dtype=torch.int64, device=table.device)
+    if top is None:
+        top = torch.empty((Q, max(k, 1), 2), dtype=torch.int32, device=table.device)
+    elif top.dtype != torch.int32 or top.numel() != Q * k * 2 or not top.is_contiguous():
+        raise HipError("fern_search: top int32 [Q,k,2]")
+    rows = torch.empty((Q, max(n_upper, 1)), dtype=torch.int32, device=table.device) if with_rows else None
+    _check(lib().bf_fern_search(_ptr(table), c_int(capacity), c_int(words * 8), _ptr(n), c_int(n_upper),
+                                _ptr(queries.contiguous()), c_int(Q), c_int(k), _ptr(part), _ptr(top), _ptr(rows), _stream()),
+           "bf_fern_search")
+    return (top, rows) if with_rows else top
+
+
+def _fern_append_work(table, n, code, best, threshold, pose, frame, poses, ids, counters):
+    return dict(kind="fern_append"), 0.0, float(table.shape[1]) * 8 + 76
+
+
+@_timed(_fern_append_work)
+def fern_append(table, n, code, best, threshold, pose, frame, poses, ids, counters):
+    """the conditional append of one code (bf_fern_append): `code` int32 [F/8] joins row n of table when
+    n == 0 or best[0] (int32 on the device, the nearest distance of the search) > threshold; pose (host
+    f32 [4,4]) and frame go to row n of poses f32 [capacity,16] and ids int32 [capacity]; counters
+    int32 [3] (FERN_COUNTERS).  Launches only"""
+    for t, dt, name in ((table, torch.int32, "table"), (n, torch.int32, "n"), (code, torch.int32, "code"),
+                        (best, torch.int32, "best"), (poses, torch.float32, "poses"), (ids, torch.int32, "ids"),
+                        (counters, torch.int32, "counters")):
+        _need(t, dt, f"fern_append: {name}")
+        if t.device != table.device:
+            raise HipError(f"fern_append: {name} on the table's device")
+    capacity, words = table.shape
+    if code.numel() != words or best.numel() < 1 or poses.numel() != capacity * 16 or ids.numel() != capacity or \
+            counters.numel() < 3 or n.numel() < 1:
+        raise HipError("fern_append: code [F/8], best [>= 1], poses [capacity,16], ids [capacity], counters [3], n [1]")
+    P = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1))
+    if P.size != 16:
+        raise HipError("fern_append: pose f32 [4,4]")
+    _check(lib().bf_fern_append(_ptr(table), c_int(capacity), c_int(words * 8), _ptr(n), _ptr(code), _ptr(best),
+                                c_int(int(threshold)), P.ctypes.data_as(ctypes.POINTER(c_float)), c_int(int(frame)), _ptr(poses),
+                                _ptr(ids), _ptr(counters), _stream()), "bf_fern_append")
+
+
+# ------------------------------------------------------------------------------------------
 # headless renderer (bf_render.hip)
 # ------------------------------------------------------------------------------------------
 def _render_target(name, keys):

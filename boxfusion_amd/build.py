@@ -35,6 +35,7 @@ SOURCES = {
     "bf_render.hip": EXACT,
     "bf_tsdf.hip": EXACT,
     "bf_track.hip": EXACT,
+    "bf_fern.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 

@@ -9,8 +9,8 @@ bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zl
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
 the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
 scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume), `... track scene.sens
-POSES.npy [--recover-lost | --from-scratch] [--photometric]` poses from tracking the depth frames against that TSDF
-(tracking.track_sequence; for `SensFrameStream(poses=...)`) and `... render
+POSES.npy [--recover-lost | --from-scratch] [--photometric] [--relocalise]` poses from tracking the depth frames
+against that TSDF (tracking.track_sequence; for `SensFrameStream(poses=...)`) and `... render
 scene.sens OUT_DIR [--boxes SEQ_boxes.pkl] [--mesh]` orbit and top-down PNG views of the cloud, or with
 --mesh of the TSDF surface (no model needed).
 
@@ -331,19 +331,22 @@ def mesh(sens, voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth
 
 
 def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth=10.0,
-          capacity=1 << 16, device="cuda", batch=16, photometric=False, **tracker_args):
+          capacity=1 << 16, device="cuda", batch=16, photometric=False, relocalise=False, ferns=512, fern_cell=16,
+          harvest=0.15, **tracker_args):
     """poses for the frames start, start + step, ... below stop by tracking.track_sequence: mode
     "recover-lost" keeps the file's finite poses and tracks the frames written as -inf; "from-scratch"
     starts at the first selected frame's pose (identity if it has none) and tracks every later frame.
     photometric=True adds the colour frames' intensity residual to the depth ICP, which places views
-    that a single plane fills.
+    that a single plane fills.  relocalise=True keeps fern keyframes of the placed frames
+    (tracking.Relocaliser with ferns, fern_cell and harvest) and restarts the tracker from the nearest
+    ones when a frame is lost from the last good pose, e.g. after the camera moved on while it was lost.
     The selected frames are decoded first and held on the device (2.1 MB per 480 x 640 frame): --step /
     --stop bound that for a long capture.
     Returns (poses f32 [num_frames,4,4]: the file's with the selected frames replaced, -inf where a
     frame stayed lost; the frame indices; info per selected frame; the TsdfVolume)"""
     import torch
     from boxfusion_amd.scene_mesh import TsdfVolume
-    from boxfusion_amd.tracking import track_sequence
+    from boxfusion_amd.tracking import Relocaliser, track_sequence
     if mode not in ("recover-lost", "from-scratch"):
         raise ValueError("mode: 'recover-lost' or 'from-scratch'")
     stream = SensFrameStream(sens, device=device, batch=batch, start=start, stop=stop, step=step)
@@ -361,19 +364,24 @@ def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=N
         colours.append(sample["wide"]["image"][-1].permute(1, 2, 0).contiguous())
     first = s.poses[ids[0]] if np.isfinite(s.poses[ids[0]]).all() else np.eye(4, dtype=np.float32)
     known = s.poses[ids] if mode == "recover-lost" else None
-    got, infos = track_sequence(torch.stack(depths), K, first_pose=first, known_poses=known, volume=vol,
-                                colours=torch.stack(colours), photometric=photometric, **tracker_args)
+    depths = torch.stack(depths)
+    rl = Relocaliser(depths.shape[1], depths.shape[2], device, ferns=ferns, cell=fern_cell, harvest=harvest,
+                     max_depth=min(max_depth, 65.535)) if relocalise else None
+    got, infos = track_sequence(depths, K, first_pose=first, known_poses=known, volume=vol, colours=torch.stack(colours),
+                                photometric=photometric, relocaliser=rl, **tracker_args)
     poses[ids] = got
     return poses, ids, infos, vol
 
 
-def track_line(file_poses, poses, ids, infos):
-    """`sens track`'s summary: frames tracked / lost and, over the tracked frames for which the file has
-    a finite pose, the RMS translation difference after moving the first selected frame onto the
-    file's pose of it"""
+def track_line(file_poses, poses, ids, infos, relocalise=False):
+    """`sens track`'s summary: frames tracked / lost (with relocalise=True also how many of the tracked
+    came back by relocalisation) and, over the tracked frames for which the file has a finite pose, the
+    RMS translation difference after moving the first selected frame onto the file's pose of it"""
     tracked = [i for i, f in zip(ids, infos) if f.get("tracked") and not f["lost"]]
     lost = [i for i, f in zip(ids, infos) if f["lost"]]
     line = f"{len(ids)} frames: {len(tracked)} tracked, {len(lost)} lost"
+    if relocalise:
+        line += f", {sum(1 for f in infos if f.get('relocalised'))} relocalised"
     both = [i for i in tracked if np.isfinite(file_poses[i]).all()]
     if ids and both and np.isfinite(file_poses[ids[0]]).all() and np.isfinite(poses[ids[0]]).all():
         align = file_poses[ids[0]].astype(np.float64) @ np.linalg.inv(poses[ids[0]].astype(np.float64))
@@ -424,6 +432,14 @@ def parser():
     pt.add_argument("--photometric", action="store_true",
                     help="track with the colour frames too (an intensity residual against the last placed frame): "
                          "places a textured wall, floor or table top that fills the view")
+    pt.add_argument("--relocalise", action="store_true",
+                    help="keep fern keyframes of the placed frames and restart the tracker from the nearest ones when a "
+                         "frame is lost from the last good pose")
+    pt.add_argument("--ferns", type=int, default=512, help="--relocalise: ferns per code, a multiple of 8")
+    pt.add_argument("--fern-cell", type=int, default=16, help="--relocalise: the cell of the block means in pixels, 1 .. 64")
+    pt.add_argument("--harvest", type=float, default=0.15,
+                    help="--relocalise: a frame becomes a keyframe when more than this share of its ferns differs from "
+                         "the nearest keyframe's")
     add_volume_arguments(pt)
     pr = sub.add_parser("render", help="write orbit and top-down PNG views of the scene's point cloud (and boxes)")
     pr.add_argument("sens")
@@ -458,6 +474,13 @@ def main(argv=None):
         check_volume_arguments(p, a)
         if not os.path.isfile(a.sens):
             p.error(f"{a.sens} is missing")
+    if a.cmd == "track" and a.relocalise:
+        if a.ferns < 8 or a.ferns % 8:
+            p.error("--ferns must be a positive multiple of 8")
+        if not 1 <= a.fern_cell <= 64:
+            p.error("--fern-cell must be 1 .. 64")
+        if not 0 <= a.harvest <= 1:
+            p.error("--harvest must be within 0 .. 1")
     with SensFile(a.sens) as s:
         if a.cmd == "info":
             info(s)
@@ -474,9 +497,10 @@ def main(argv=None):
         elif a.cmd == "track":
             mode = "from-scratch" if a.from_scratch else "recover-lost"
             poses, ids, infos, vol = track(s, mode, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth,
-                                           a.capacity, photometric=a.photometric)
+                                           a.capacity, photometric=a.photometric, relocalise=a.relocalise, ferns=a.ferns,
+                                           fern_cell=a.fern_cell, harvest=a.harvest)
             np.save(a.poses, poses)
-            print(track_line(s.poses, poses, ids, infos) + f" -> {a.poses}")
+            print(track_line(s.poses, poses, ids, infos, a.relocalise) + f" -> {a.poses}")
             if a.mesh:
                 nv, nf = vol.save_ply(a.mesh)
                 print(f"{nv} vertices, {nf} faces -> {a.mesh}")

@@ -13,7 +13,10 @@ frame (a recording without poses) or only for the frames whose pose is not finit
 lost tracking: ScanNet writes -inf there and `SensFile.poses_filled()` repeats the last valid pose).
 
 A frame the tracker cannot place is *lost*: its pose is all -inf, the capture format's own
-convention, which `TsdfVolume.integrate`, the renderer and the GT filter already skip.
+convention, which `TsdfVolume.integrate`, the renderer and the GT filter already skip.  When the camera
+moved on while it was lost, the last good pose is no guess any more: `Relocaliser` keeps keyframes of
+the placed frames as randomised-fern codes (bf_fern.hip) and restarts the tracker from the poses of
+the keyframes nearest to the lost frame's code.
 """
 from __future__ import annotations
 
@@ -175,8 +178,148 @@ class IcpTracker:
         return pose, info
 
 
+def fern_table(ferns, cells, seed=0, depth_range_m=(0.4, 4.0)):
+    """the randomised ferns of a Relocaliser: i32 [ferns, 5] of (cell index below `cells`, the thresholds of R, G
+    and B in grey levels 0 .. 254, the depth threshold in millimetres within depth_range_m), drawn from
+    numpy.random.default_rng(seed): the same table for the same arguments"""
+    ferns, cells = int(ferns), int(cells)
+    lo, hi = (int(round(float(v) * 1000.0)) for v in depth_range_m)
+    if ferns < 8 or ferns % 8:
+        raise ValueError("fern_table: ferns a positive multiple of 8")
+    if cells < 1 or not 0 <= lo < hi <= 65535:
+        raise ValueError("fern_table: at least one cell and 0 <= depth_range_m[0] < depth_range_m[1] <= 65.535")
+    rng = np.random.default_rng(seed)
+    table = np.empty((ferns, 5), np.int32)
+    table[:, 0] = rng.integers(0, cells, ferns)
+    table[:, 1:4] = rng.integers(0, 255, (ferns, 3))
+    table[:, 4] = rng.integers(lo, hi, ferns)
+    return table
+
+
+class Relocaliser:
+    """keyframe relocalisation with randomised ferns (Glocker et al.; bf_fern.hip) for frames of H x W.
+
+    Every placed frame is offered to `observe`: its depth (and colour) means over cells of `cell` pixels
+    are compared with `ferns` random thresholds (`fern_table`: seed, depth_range in metres) into a code
+    of four bits per fern; the code joins the keyframe table, with the frame's pose, when more than
+    floor(harvest * ferns) of its ferns differ from the nearest keyframe's (or the table is empty); a
+    table of `capacity` keyframes that is full counts the frame and drops it.  `query` returns the
+    nearest keyframes of a frame, `relocalise` restarts an IcpTracker from their poses.  Without images
+    the colour bits are 0 in the table and the query alike and the distance counts the depth bits only;
+    use the same choice for every call.  max_depth (<= 65.535) is the depth beyond which a pixel is
+    invalid, as in TsdfVolume.
+
+    The defaults of harvest and of relocalise's max_distance come from the range the literature uses
+    and from a 48 x 64 synthetic room; nobody has measured them on a real capture."""
+
+    def __init__(self, H, W, device, ferns=512, cell=16, capacity=4096, harvest=0.15, seed=0, depth_range=(0.4, 4.0),
+                 max_depth=10.0):
+        self.H, self.W, self.device = int(H), int(W), torch.device(device)
+        self.ferns, self.cell, self.capacity = int(ferns), int(cell), int(capacity)
+        if self.ferns < 8 or self.ferns % 8:
+            raise ValueError("Relocaliser: ferns a positive multiple of 8")
+        if not 1 <= self.cell <= 64 or self.H // self.cell < 1 or self.W // self.cell < 1:
+            raise ValueError("Relocaliser: 1 <= cell <= 64, and no larger than the image")
+        if self.capacity < 1 or not 0 <= float(harvest) <= 1 or not 0 < float(max_depth) <= 65.535:
+            raise ValueError("Relocaliser: capacity >= 1, 0 <= harvest <= 1, 0 < max_depth <= 65.535")
+        self.max_depth, self.harvest = float(max_depth), float(harvest)
+        self.threshold = int(np.floor(self.harvest * self.ferns))
+        self.cells = (self.H // self.cell) * (self.W // self.cell)
+        self.table = fern_table(self.ferns, self.cells, seed, depth_range)
+        self._ferns = _lib.fern_upload(self.table, self.cells, self.device)
+        words = self.ferns // 8
+        self._codes = torch.zeros((self.capacity, words), dtype=torch.int32, device=self.device)
+        self._poses = torch.zeros((self.capacity, 16), dtype=torch.float32, device=self.device)
+        self._ids = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        self._state = torch.zeros(4, dtype=torch.int32, device=self.device)        # n, then _lib.FERN_COUNTERS
+        self._code = torch.empty((1, words), dtype=torch.int32, device=self.device)
+        self._best = torch.empty((1, 1, 2), dtype=torch.int32, device=self.device)
+        self._offered = 0                                    # the host's bound of n: the frames observe has passed on
+
+    def _frame(self, depth, rgb, who):
+        """(depth f32 [H,W], rgb u8 [H,W,3] or None) on the device; an image of another size is resized as
+        TsdfVolume.integrate does"""
+        depth = depth if torch.is_tensor(depth) else _lib.h2d(np.asarray(depth, np.float32), self.device)
+        depth = depth.to(self.device, torch.float32)
+        if tuple(depth.shape) != (self.H, self.W):
+            raise ValueError(f"{who}: depth [{self.H},{self.W}], got {tuple(depth.shape)}")
+        if rgb is not None:
+            rgb = rgb if torch.is_tensor(rgb) else _lib.h2d(np.asarray(rgb), self.device)
+            rgb = rgb.to(self.device)
+            if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+                raise ValueError(f"{who}: rgb u8 [Hc,Wc,3], got {rgb.dtype} {tuple(rgb.shape)}")
+            if tuple(rgb.shape[:2]) != (self.H, self.W):
+                rgb = _lib.resize_bicubic_u8(rgb, self.H, self.W)
+        return depth, rgb
+
+    def __len__(self):
+        return int(self._state[0].item())
+
+    def observe(self, depth, pose, rgb=None, frame=-1):
+        """offer a placed frame (depth f32 [H,W] metres, camera-to-world pose [4,4], rgb u8 [Hc,Wc,3] or None,
+        its frame id): four launches and no synchronisation; a pose with a non-finite entry is ignored"""
+        pose = np.asarray(pose.cpu() if torch.is_tensor(pose) else pose, np.float32).reshape(4, 4)
+        if not np.isfinite(pose).all():
+            return
+        depth, rgb = self._frame(depth, rgb, "observe")
+        _lib.fern_encode(depth, rgb, self.cell, self.max_depth, self._ferns, codes=self._code)
+        _lib.fern_search(self._codes, self._state[:1], min(max(self._offered, 1), self.capacity), self._code, 1, top=self._best)
+        _lib.fern_append(self._codes, self._state[:1], self._code[0], self._best[0, 0], self.threshold, pose, frame,
+                         self._poses, self._ids, self._state[1:])
+        self._offered += 1
+
+    def query(self, depth, rgb=None, k=4):
+        """the k (<= 8) nearest keyframes of a frame, nearest first: [(distance in ferns, keyframe index, its
+        pose f32 [4,4], its frame id)], fewer when the table holds fewer; one read-back"""
+        k = int(k)
+        if not 1 <= k <= _lib.FERN_K_MAX:
+            raise ValueError(f"query: 1 <= k <= {_lib.FERN_K_MAX}")
+        depth, rgb = self._frame(depth, rgb, "query")
+        _lib.fern_encode(depth, rgb, self.cell, self.max_depth, self._ferns, codes=self._code)
+        top = _lib.fern_search(self._codes, self._state[:1], min(max(self._offered, 1), self.capacity), self._code, k)[0]
+        at = top[:, 1].clamp(min=0).long()
+        # integers below 2^31 and f32 poses: exact in f64, so one row comes back
+        row = torch.cat([top.double(), self._poses[at].double(), self._ids[at].double()[:, None]], 1).cpu().numpy()
+        return [(int(r[0]), int(r[1]), r[2:18].astype(np.float32).reshape(4, 4), int(r[18])) for r in row if r[1] >= 0]
+
+    def relocalise(self, tracker, depth, rgb=None, k=4, max_distance=0.5):
+        """place a frame the tracker has lost: the nearest k keyframes whose distance is at most max_distance *
+        ferns, nearest first, each as the guess of tracker.track(depth, pose) (without the image: the
+        tracker's photometric reference is the last placed frame, somewhere else, so the geometric gates
+        verify); the first that places the frame wins.  With rgb the placed frame becomes the tracker's
+        photometric reference.  Going by code distance and stopping at max_distance, instead of trying
+        every keyframe, matters: the gates alone cannot tell one corner of a box room from another.
+        -> (pose f32 [4,4] or all -inf, the tracker's info with relocalised, candidates_tried and, when
+        placed, keyframe and fern_distance)"""
+        info = dict(lost=True, iterations=0, inliers=0, sampled=0, rms=float("inf"), cond=float("inf"))
+        tried = 0
+        for distance, keyframe, guess, _ in self.query(depth, rgb, k):
+            if distance > max_distance * self.ferns:
+                break
+            tried += 1
+            pose, info = tracker.track(depth, guess)
+            if not info["lost"]:
+                if rgb is not None:
+                    tracker.set_reference(rgb, depth, pose)
+                info.update(relocalised=True, keyframe=keyframe, fern_distance=distance, candidates_tried=tried)
+                return pose, info
+        info.update(lost=True, relocalised=False, candidates_tried=tried)
+        return LOST.copy(), info
+
+    def keyframes(self):
+        """(poses f32 [n,4,4], frame ids i32 [n], codes u32 [n, ferns/8]) of the table, read back"""
+        n = len(self)
+        return (self._poses[:n].cpu().numpy().reshape(n, 4, 4), self._ids[:n].cpu().numpy(),
+                self._codes[:n].cpu().numpy().view(np.uint32))
+
+    def counters(self):
+        """dict(keyframes, observed, added, dropped_full), read back"""
+        s = self._state.cpu().tolist()
+        return dict(keyframes=s[0], **dict(zip(_lib.FERN_COUNTERS, s[1:])))
+
+
 def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, colours=None, photometric=False,
-                   **tracker_args):
+                   relocaliser=None, **tracker_args):
     """track and fuse a run of depth frames (depths f32 [N,H,W] metres, tensor or array) into `volume`
     (a scene_mesh.TsdfVolume): frame 0 is integrated at its pose (known_poses[0], or without known_poses
     first_pose, default identity); every later frame takes its known finite pose, or is tracked from
@@ -185,7 +328,9 @@ def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, co
     the volume; photometric=True (which needs colours) also hands each tracked frame's image to the
     tracker, with the last frame that has a pose as the photometric reference.  Returns (poses f32
     [N,4,4] with -inf for lost frames, info per frame; info['tracked'] says whether the pose came from
-    the tracker)."""
+    the tracker).  relocaliser (a Relocaliser for H x W): every frame that ends up with a pose is offered
+    to it after it is integrated, a frame the tracker loses from the last good pose is handed to its
+    `relocalise` before it is given up, and every info gains `relocalised`."""
     if volume is None:
         raise ValueError("track_sequence: volume=TsdfVolume(...) is required")
     depths = torch.as_tensor(depths)
@@ -214,6 +359,11 @@ def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, co
         else:
             pose, info = tracker.track(depths[i], last, colours[i]) if photometric else tracker.track(depths[i], last)
             info["tracked"] = True
+            if relocaliser is not None and info["lost"]:
+                pose, info = relocaliser.relocalise(tracker, depths[i], None if colours is None else colours[i])
+                info["tracked"] = True
+        if relocaliser is not None:
+            info.setdefault("relocalised", False)
         infos.append(info)
         poses[i] = pose
         if info["lost"]:
@@ -221,5 +371,7 @@ def track_sequence(depths, K, first_pose=None, known_poses=None, volume=None, co
         volume.integrate(depths[i], K, pose[None], None if colours is None else colours[i])
         if photometric and not info.get("tracked"):
             tracker.set_reference(colours[i], depths[i], pose)
+        if relocaliser is not None:
+            relocaliser.observe(depths[i], pose, None if colours is None else colours[i], i)
         last = pose
     return poses, infos

@@ -994,6 +994,46 @@ int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H
                     double dist_max, double intensity_max, double* partials, double* out,
                     void* stream);
 
+/* ---- relocalisation: randomised ferns over a frame's cell means, a keyframe table of codes ---------
+ * A frame is depth f32 [H,W] metres and, optionally, rgb u8 [H,W,3].  With cell size c (1 .. 64) the
+ * grid is Hc = H / c by Wc = W / c cells of n = c^2 pixels (the remainder rows and columns are
+ * ignored; no cell at all is BF_ERR_ARG).  Colour mean per channel: (2 S + n) / (2 n) of the sum S, in
+ * integer division; 0 without an image.  Depth: a pixel is valid when 0 < d < max_depth (NaN fails;
+ * max_depth <= 65.535) and contributes rint(d * 1000.0f) millimetres, half to even; with m valid
+ * pixels of sum Sd the cell's mean is (2 Sd + m) / (2 m) when 2 m >= n, else -1.
+ *
+ * bf_fern_encode: B frames -> means i32 [B, Hc Wc, 4] (R, G, B, D; NULL to skip) and codes u32
+ * [B, F / 8] (NULL to skip; one of the two is required).  ferns i32 [F, 5] on the device, F a multiple
+ * of 8: per fern a cell index and the thresholds tR, tG, tB (grey levels) and tD (millimetres).  Fern
+ * f's nibble (R > tR) | (G > tG) << 1 | (B > tB) << 2 | (D >= 0 && D > tD) << 3 at its cell goes to
+ * bits 4 (f mod 8) of word f / 8.  A cell index outside the grid gives nibble 0 and reads no pixel;
+ * bf_fern_table_check (host table, before the upload) refuses such a table with BF_ERR_ARG.
+ *
+ * bf_fern_search: the distance of two codes is the number of ferns whose nibbles differ (per word
+ * x = a ^ b, popcount of (x | x >> 1 | x >> 2 | x >> 3) & 0x11111111).  table u32 [capacity, F / 8];
+ * n i32 [1] on the device, the keyframes held; n_upper (host, n <= n_upper <= capacity) sizes the
+ * grid; queries u32 [Q, F / 8]; k <= 8.  top i32 [Q, k, 2]: the k smallest (distance, index) by
+ * distance, then index, (-1, -1) beyond n.  rows i32 [Q, n_upper] or NULL: every distance, -1 at and
+ * beyond n.  part int64 [Q, bf_fern_search_blocks(n_upper), k] is workspace.  Integers only: the same
+ * bits on every call.
+ *
+ * bf_fern_append: with best i32 [>= 1] on the device (the nearest distance bf_fern_search wrote for
+ * this code), the code (u32 [F / 8], device) joins row n of the table when n == 0 or best[0] >
+ * threshold (in ferns); pose_host (f32 [16], host, passed by value) goes to row n of poses f32
+ * [capacity, 16], frame to ids i32 [capacity], and n becomes n + 1.  A full table changes nothing but
+ * the counter.  counters i32 [3], added to: observed, added, dropped_full.  No read-back. */
+int bf_fern_table_check(const int32_t* ferns_host, int F, int cells);
+int bf_fern_encode(const float* depth, const uint8_t* rgb, int B, int H, int W, int cell,
+                   float max_depth, const int32_t* ferns, int F, int32_t* means, uint32_t* codes,
+                   void* stream);
+int bf_fern_search_blocks(int n_upper);
+int bf_fern_search(const uint32_t* table, int capacity, int F, const int32_t* n, int n_upper,
+                   const uint32_t* queries, int Q, int k, long long* part, int32_t* top,
+                   int32_t* rows, void* stream);
+int bf_fern_append(uint32_t* table, int capacity, int F, int32_t* n, const uint32_t* code,
+                   const int32_t* best, int threshold, const float* pose_host, int frame,
+                   float* poses, int32_t* ids, int32_t* counters, void* stream);
+
 /* placement probe (diagnostic): n_wg workgroups on `stream`, each spinning `spin` cycles, write
  * out[2b] = HW_ID (CU bits 11:8, SH 12, SE 15:13) and out[2b+1] = XCC id -- which CUs a (CU-masked)
  * stream really runs on */

@@ -11,6 +11,11 @@
   track        IcpTracker.track of the next room frame from the pose before it: wall-clock of the whole call, the
                raycast, the twelve reductions, their read-backs and the host's 6 x 6 solves included
   track_rgb    the same call with the frame's image: bf_grey_u8 and twelve bf_photo_reduce more, one read-back each
+  fern_encode  bf_fern_encode (cell 16, 512 ferns) of one room frame with its image, and of a batch of eight
+  fern_search  bf_fern_search (both kernels, k = 4) of one code against 256 and against 4096 random keyframes
+  observe      Relocaliser.observe of a room frame: encode, search with k = 1 and the conditional append
+  relocalise   Relocaliser.relocalise of the next room frame with the four fused frames as keyframes: wall-clock of
+               the query, its read-back and the tracker's call from the nearest keyframe's pose
 
 Device times are the median of REPS runs between device events after a warm-up, with their min and max; the
 wall-clock is the median of REPS calls, each followed by a synchronisation.  --scale shrinks the image for a
@@ -29,7 +34,7 @@ sys.path.insert(0, ROOT)
 from boxfusion_amd import _lib  # noqa: E402
 from boxfusion_amd.scene_mesh import TsdfVolume  # noqa: E402
 from boxfusion_amd.synthetic import SCANNET_K, Scene  # noqa: E402
-from boxfusion_amd.tracking import IcpTracker, world_to_camera  # noqa: E402
+from boxfusion_amd.tracking import IcpTracker, Relocaliser, world_to_camera  # noqa: E402
 
 REPS = 9
 LO, HI = np.array([-2.0, -1.7, -1.3]), np.array([2.0, 1.8, 1.3])
@@ -166,6 +171,40 @@ def main():
             out[name].update(photo_inlier_share=round(info["photo_inliers"] / max(info["sampled"], 1), 3),
                              photo_rms=round(info["photo_rms"], 5))
         print(name, out[name], flush=True)
+
+    cell = 16 if min(H, W) >= 64 else 4
+    rl = Relocaliser(H, W, dev, ferns=512, cell=cell, max_depth=room.max_depth)
+    all_rgbs = [torch.from_numpy(room_image(room_poses[i], K, room_depths[i].cpu().numpy())).to(dev) for i in range(5)]
+    one_d, one_c = room_depths[4][None].contiguous(), all_rgbs[4][None].contiguous()
+    eight_d, eight_c = one_d.repeat(8, 1, 1), one_c.repeat(8, 1, 1, 1)
+    for name, d, c in (("fern_encode_1", one_d, one_c), ("fern_encode_8", eight_d, eight_c)):
+        out[name] = device_ms(lambda: _lib.fern_encode(d, c, cell, room.max_depth, rl._ferns))
+        print(name, out[name], flush=True)
+    rng = np.random.default_rng(0)
+    table = torch.from_numpy(rng.integers(0, 1 << 32, (4096, 64), dtype=np.uint64).astype(np.uint32).view(np.int32)).to(dev)
+    code = _lib.fern_encode(one_d, one_c, cell, room.max_depth, rl._ferns)
+    for n in (256, 4096):
+        held = torch.tensor([n], dtype=torch.int32, device=dev)
+        out[f"fern_search_{n}"] = device_ms(lambda: _lib.fern_search(table, held, n, code, 4))
+        print(f"fern_search {n}", out[f"fern_search_{n}"], flush=True)
+    for i in range(4):
+        rl.observe(room_depths[i], room_poses[i], all_rgbs[i], i)
+    out["observe"] = device_ms(lambda: rl.observe(room_depths[4], room_poses[4], all_rgbs[4], 4))
+    out["observe"].update(rl.counters())
+    print("observe", out["observe"], flush=True)
+    walls = []
+    for _ in range(REPS + 1):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        pose, info = rl.relocalise(tracker, room_depths[4], all_rgbs[4])
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t) * 1e3)
+    walls = walls[1:]
+    err = float(np.linalg.norm(pose[:3, 3] - room_poses[4][:3, 3])) if not info["lost"] else None
+    out["relocalise"] = dict(wall_ms=round(float(np.median(walls)), 3), min=round(min(walls), 3), max=round(max(walls), 3),
+                             lost=info["lost"], candidates_tried=info["candidates_tried"], keyframe=info.get("keyframe"),
+                             fern_distance=info.get("fern_distance"), translation_error_m=err)
+    print("relocalise", out["relocalise"], flush=True)
     print(json.dumps(out))
 
 
