@@ -310,6 +310,13 @@ def nms_scan(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_n
     return keep, succ, events, counts
 
 
+def nms_scan_form(n, list_capacity, has_workspace=True):
+    """the scan bf_nms_scan_ws launches (bf_nms_scan_form): 0 one wave on the IoU matrix, 1 one
+    wave on the bit masks, 2 block scan with the IoU matrix in LDS, 3 block scan reading it from
+    global memory; nms_scan always passes a workspace, bf_nms_scan none"""
+    return int(lib().bf_nms_scan_form(c_int(n), c_int(list_capacity), c_int(int(bool(has_workspace)))))
+
+
 def corr_assoc(corners, dims, scores, boxes2d, init_id, cam_poses, cur_pose, K, n_glo, mask,
                success, fl_items, fl_len, valid_num, cfg: CorrCfg, out=None):
     """returns device tensors keep, events, counts (n_keep, n_events, status); `out` as nms_scan"""

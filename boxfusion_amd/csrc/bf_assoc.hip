@@ -561,6 +561,15 @@ BF_API size_t bf_nms_scan_workspace_size(int n) {
     return n > 0 ? sizeof(unsigned long long) * 2 * (size_t)n * nms_words(n) : 0;
 }
 
+// which scan bf_nms_scan_ws launches for n boxes at a list capacity, with or without a workspace:
+// 0 one wave on the IoU matrix in LDS, 1 one wave on the threshold bit masks, 2 the block scan
+// with the IoU matrix in LDS, 3 the block scan reading it from global memory
+BF_API int bf_nms_scan_form(int n, int list_capacity, int has_workspace) {
+    if (n <= NMS_FAST_N && nms_fast_lds(n, list_capacity, false) <= NMS_FAST_LDS_MAX) return 0;
+    if (has_workspace && nms_fast_lds(n, list_capacity, true) <= NMS_FAST_LDS_MAX) return 1;
+    return (size_t)n * n <= NMS_IOU_LDS_MAX ? 2 : 3;
+}
+
 BF_API int bf_nms_scan(const double* iou, const float* corners, const float* scores,
                        const int32_t* init_id, const float* cam_poses, int n, int32_t* fl_items,
                        int32_t* fl_len, float* valid_num, int32_t* keep, int32_t* n_keep,
@@ -590,13 +599,14 @@ BF_API int bf_nms_scan_ws(const double* iou, const float* corners, const float* 
         attr_w = true;
     }
     hipStream_t st = bf_stream(stream);
-    if (n <= NMS_FAST_N && nms_fast_lds(n, cfg->list_capacity, false) <= NMS_FAST_LDS_MAX) {
+    const int form = bf_nms_scan_form(n, cfg->list_capacity, workspace != nullptr);
+    if (form == 0) {
         hipLaunchKernelGGL(k_nms_scan_w<false>, dim3(1), dim3(64), nms_fast_lds(n, cfg->list_capacity, false),
                            st, iou, corners, scores, init_id, cam_poses, n, fl_items, fl_len, valid_num,
                            keep, n_keep, success, n_success, events, n_events, status, *cfg, nullptr);
         return bf_check_launch();
     }
-    if (workspace && nms_fast_lds(n, cfg->list_capacity, true) <= NMS_FAST_LDS_MAX) {
+    if (form == 1) {
         const int words = nms_words(n);
         auto* bits = static_cast<unsigned long long*>(workspace);
         hipLaunchKernelGGL(k_nms_bits, dim3(bf_cdiv(n * words, 4)), dim3(256), 0, st, iou, n, words,
@@ -607,7 +617,7 @@ BF_API int bf_nms_scan_ws(const double* iou, const float* corners, const float* 
         return bf_check_launch();
     }
     size_t lds = sizeof(int) * (size_t)(5 * n + 8) + sizeof(float) * 3 * (size_t)n;
-    if ((size_t)n * n <= NMS_IOU_LDS_MAX) lds += sizeof(double) * (size_t)n * n;
+    if (form == 2) lds += sizeof(double) * (size_t)n * n;
     static bool attr_set = false;
     if (!attr_set) {
         const size_t big = sizeof(int) * (5 * BF_MAX_BOXES + 8) + sizeof(float) * 3 * BF_MAX_BOXES;
@@ -834,6 +844,16 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_corr_assoc(
     }
 }
 
+// no box to visit: the kernel is not launched, its two counts are still written (status is only
+// ever OR-ed into and stays as it is)
+static int corr_nothing_kept(int32_t* n_keep_out, int32_t* n_events, void* stream) {
+    if (!n_keep_out || !n_events) return BF_ERR_ARG;
+    hipStream_t st = bf_stream(stream);
+    return hipMemsetAsync(n_keep_out, 0, sizeof(int32_t), st) == hipSuccess &&
+                   hipMemsetAsync(n_events, 0, sizeof(int32_t), st) == hipSuccess
+               ? BF_OK : BF_ERR_LAUNCH;
+}
+
 BF_API int bf_corr_assoc(const float* corners, const float* dims, const float* scores,
                          const float* boxes2d, const int32_t* init_id, const float* cam_poses,
                          const float* cur_pose, const float* K, int n_all, int n_glo,
@@ -843,10 +863,7 @@ BF_API int bf_corr_assoc(const float* corners, const float* dims, const float* s
                          const bf_corr_cfg* cfg, void* stream) {
     if (!cfg || n_all < 0 || n_mask < 0 || n_success < 0) return BF_ERR_ARG;
     if (n_all > BF_MAX_BOXES || n_mask > BF_MAX_BOXES) return BF_ERR_CAPACITY;
-    if (n_mask == 0) {
-        return hipMemsetAsync(n_keep_out, 0, sizeof(int32_t), bf_stream(stream)) == hipSuccess
-                   ? BF_OK : BF_ERR_LAUNCH;
-    }
+    if (n_mask == 0) return corr_nothing_kept(n_keep_out, n_events, stream);
     size_t lds = sizeof(double) * 4 * (size_t)(n_mask + 1) + sizeof(int) * 2 * (size_t)(n_mask + 1) +
                  (size_t)n_mask + 16;
     hipLaunchKernelGGL(k_corr_assoc, dim3(1), dim3(SCAN_THREADS), lds, bf_stream(stream), corners,
@@ -868,10 +885,7 @@ BF_API int bf_corr_assoc_chained(const float* corners, const float* dims, const 
                                  const bf_corr_cfg* cfg, void* stream) {
     if (!cfg || n_all < 0 || !n_mask_dev || !n_success_dev || !mask || !success) return BF_ERR_ARG;
     if (n_all > BF_MAX_BOXES) return BF_ERR_CAPACITY;
-    if (n_all == 0) {
-        return hipMemsetAsync(n_keep_out, 0, sizeof(int32_t), bf_stream(stream)) == hipSuccess
-                   ? BF_OK : BF_ERR_LAUNCH;
-    }
+    if (n_all == 0) return corr_nothing_kept(n_keep_out, n_events, stream);
     const int n_mask = n_all;   // nms keep <= n_all
     size_t lds = sizeof(double) * 4 * (size_t)(n_mask + 1) + sizeof(int) * 2 * (size_t)(n_mask + 1) +
                  (size_t)n_mask + 16;

@@ -159,6 +159,14 @@ int bf_nms_scan_ws(const double* iou, const float* corners, const float* scores,
                    int32_t* events, int32_t* n_events, int32_t* status,
                    const bf_nms_cfg* cfg, void* workspace, void* stream);
 
+/* The scan bf_nms_scan_ws launches for n boxes at cfg->list_capacity (host only, no launch):
+ *   0  one wave, IoU matrix in LDS (n <= 96 and every operand fits in LDS)
+ *   1  one wave on the threshold bit masks (needs the workspace; operands fit in LDS)
+ *   2  256-thread block scan, IoU matrix staged in LDS (n <= 120)
+ *   3  256-thread block scan, IoU matrix read from global memory
+ * has_workspace: nonzero when a workspace is passed (bf_nms_scan passes none). */
+int bf_nms_scan_form(int n, int list_capacity, int has_workspace);
+
 /* ------------------------------------------------------------------------------------------
  * Cross-view correspondence association for small boxes
  *   Instances3D.correspondence_association (instances.py:411-490) + project_3d_to_2d_box
@@ -180,7 +188,8 @@ typedef struct {
  *   K f32[3,3]; mask i32[n_mask] = sorted NMS keep; success i32[n_success] = sorted success_nms.
  *   In/out: fl_items/fl_len (fusion lists), valid_num f32[n_all].
  *   Out: keep_out i32[n_mask] sorted, n_keep_out i32[1], events i32[n_all,3], n_events,
- *        status i32[1]. */
+ *        status i32[1] (OR-ed into).  With n_mask == 0 (bf_corr_assoc_chained: n_all == 0) no
+ *        kernel runs; n_keep_out and n_events are still written, both 0. */
 int bf_corr_assoc(const float* corners, const float* dims, const float* scores,
                   const float* boxes2d, const int32_t* init_id, const float* cam_poses,
                   const float* cur_pose, const float* K, int n_all, int n_glo,

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import oracle as OR
+from tests import assoc_cases as AC
 from tests import trace_util as TU
 
 pytestmark = pytest.mark.gpu
@@ -99,7 +100,7 @@ class HipBackend:
                                        it, ln, vn, self.ccfg)
         c = cnt.cpu().numpy()
         assert c[2] == 0
-        return dict(keep=k.cpu().numpy()[:c[0]],
+        return dict(keep=k.cpu().numpy()[:c[0]], events=ev.cpu().numpy()[:c[1]],
                     fusion_list=OR.unpack_lists(it.cpu().numpy(), ln.cpu().numpy(),
                                                 len(fusion_list)),
                     valid_num=vn.cpu().numpy())
@@ -121,17 +122,39 @@ class HipBackend:
         return o
 
 
+class OracleCheckedBackend(HipBackend):
+    """HipBackend whose correspondence step is also compared with OR.corr_assoc on the same
+    inputs: the events (which the replay itself does not see) and all of valid_num"""
+    corr_calls = corr_events = 0
+
+    def corr(self, *a):
+        got = super().corr(*a)
+        ref = OR.corr_assoc(*a, AC.as_cfg(OR.CorrCfg, self.ccfg))
+        assert ref["status"] == 0
+        for k in ("keep", "events", "valid_num"):
+            np.testing.assert_array_equal(got[k], ref[k], err_msg=f"corr {k}")
+        assert got["fusion_list"] == ref["fusion_list"]
+        self.corr_calls += 1
+        self.corr_events += len(ref["events"])
+        return got
+
+
 @pytest.mark.parametrize("name", TU.TRACES)
 def test_trace_replay_hip(L, name):
     """NMS keep/success, fusion lists, association and fused boxes bit-exact vs the reference
     (ScanNet scene traces, the CA-1M trace at ca1m.yaml thresholds on 384 x 512 portrait frames,
-    and the overrun-free face-on trace, reference-pinned at every keyframe)."""
+    and the overrun-free face-on trace, reference-pinned at every keyframe); the correspondence
+    step's events and full valid_num of every keyframe bit-exact vs the oracle."""
     t = TU.load(name)
-    stats = TU.replay(t, HipBackend(L, False, *TU.trace_setup(t)))
-    print(name, stats)
-    assert stats["fused"] >= 10 and stats["reference_pinned"] >= 1
+    be = OracleCheckedBackend(L, False, *TU.trace_setup(t))
+    stats = TU.replay(t, be)
+    print(name, stats, "corr calls", be.corr_calls, "events", be.corr_events)
+    assert stats["fused"] >= 10 and stats["reference_pinned"] >= 1 and be.corr_calls >= 8
     if "faceon" in name:
         assert stats["reference_pinned"] == stats["keyframes"] and stats["hull_overflow_keyframes"] == 0
+        assert stats["corr_changes"] >= 2 and be.corr_events >= 2
+    if "small" in name:
+        assert stats["corr_changes"] > 5 and be.corr_events >= 40
 
 
 def test_faceon_fusion_reference_pinned(L):
@@ -413,29 +436,17 @@ def test_boxfusion_hull_overflow_policy(L):
 
 @pytest.mark.parametrize("n_glo,n_new", [(150, 25), (97, 0), (300, 40)])
 def test_nms_scan_large_vs_oracle(L, n_glo, n_new):
-    """the greedy scan + record() with more than 96 boxes (the 256-thread k_nms_scan of the
-    default build; <= 96 runs the one-wave form): ~150 global boxes plus a keyframe's new ones,
+    """the greedy scan + record() with more than 96 boxes, up to the largest count the one-wave
+    bit-mask scan (k_nms_bits + k_nms_scan_w<true>) takes at the default list capacity; <= 96 runs
+    the one-wave scan on the IoU matrix, 341 and more the 256-thread k_nms_scan
+    (tests/test_gpu_assoc.py): ~150 global boxes plus a keyframe's new ones,
     clustered so that suppressions, list merges (up to 5 views) and pose gates all occur;
     keep / success / events / fusion lists / valid_num bit-exact against the oracle"""
-    from boxfusion_amd.synthetic import Scene
-    rng = np.random.default_rng(n_glo + n_new)
     n = n_glo + n_new
-    centres = rng.uniform(-2.5, 2.5, (n // 3 + 1, 3))
-    xyz = centres[rng.integers(0, len(centres), n)] + rng.normal(0, 0.04, (n, 3))
-    lhw = rng.uniform(0.2, 0.9, (n, 3))
-    b = np.concatenate([xyz, lhw], 1).astype(np.float32)
-    yaw = rng.uniform(-0.2, 0.2, n)
-    R = np.stack([[[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
-                  for a in yaw]).astype(np.float32)
-    corners = OR.box_corners(b, R)
-    scores = rng.permutation(np.linspace(0.3, 0.99, n)).astype(np.float32)
-    init_id = np.arange(n, dtype=np.int32)
-    scene = Scene(seed=1)
-    cam_poses = np.stack([scene.pose(int(f)) for f in rng.integers(0, 1000, n)]).astype(np.float32)
-    # global boxes carry earlier merges (lists of up to 4 views), the new ones their own id
-    fusion_list = [sorted(set([i] + rng.integers(0, n_glo, rng.integers(0, 4)).tolist())) if i < n_glo
-                   else [i] for i in range(n)]
-    valid_num = rng.integers(0, 3, n).astype(np.float32)
+    assert L.nms_scan_form(n, CAP) == 1
+    c = AC.nms_case(n_glo, n_new, n_glo + n_new)
+    corners, scores, init_id, cam_poses, fusion_list, valid_num = (
+        c[k] for k in ("corners", "scores", "init_id", "cam_poses", "fusion_list", "valid_num"))
     iou = L.obb_iou_matrix(_t(corners)).cpu().numpy()
     assert (iou[np.triu_indices(n, 1)] > 0.1).sum() > n // 4
     got = HipBackend(L).nms(iou, corners, scores, init_id, cam_poses, fusion_list, valid_num)
@@ -458,6 +469,7 @@ def test_nms_scan_input_list_longer_than_capacity(L, n):
     corners = _t(OR.box_corners(b, R))
     dev = corners.device
     cap = 8
+    assert L.nms_scan_form(n, cap) == (0 if n <= 96 else 1)
     items = torch.full((n, cap), -1, dtype=torch.int32, device=dev)
     items[:, 0] = torch.arange(n, dtype=torch.int32, device=dev)
     lens = torch.ones(n, dtype=torch.int32, device=dev)
@@ -476,24 +488,13 @@ def test_nms_scan_input_list_longer_than_capacity(L, n):
 @pytest.mark.parametrize("n_glo,n_new", [(1, 0), (0, 1), (1, 1), (2, 1), (94, 1), (95, 1), (96, 1), (90, 7)])
 def test_nms_scan_small_and_boundary_vs_oracle(L, n_glo, n_new):
     """the IoU matrix + greedy scan at the smallest counts and around the 96-box switch between
-    the one-wave scan and the block scan: bit-exact against the oracle"""
-    from boxfusion_amd.synthetic import Scene
-    rng = np.random.default_rng(1000 + 17 * n_glo + n_new)
+    the one-wave scan on the IoU matrix and the one on its bit masks: bit-exact against the oracle"""
     n = n_glo + n_new
-    centres = rng.uniform(-2.0, 2.0, (max(1, n // 3), 3))
-    xyz = centres[rng.integers(0, len(centres), n)] + rng.normal(0, 0.04, (n, 3))
-    b = np.concatenate([xyz, rng.uniform(0.2, 0.9, (n, 3))], 1).astype(np.float32)
-    yaw = rng.uniform(-0.2, 0.2, n)
-    R = np.stack([[[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
-                  for a in yaw]).astype(np.float32)
-    corners = OR.box_corners(b, R)
-    scores = rng.permutation(np.linspace(0.3, 0.99, n)).astype(np.float32)
-    init_id = np.arange(n, dtype=np.int32)
-    scene = Scene(seed=2)
-    cam_poses = np.stack([scene.pose(int(f)) for f in rng.integers(0, 1000, n)]).astype(np.float32)
-    fusion_list = [sorted(set([i] + rng.integers(0, max(1, n_glo), rng.integers(0, 3)).tolist()))
-                   if i < n_glo else [i] for i in range(n)]
-    valid_num = rng.integers(0, 3, n).astype(np.float32)
+    assert L.nms_scan_form(n, CAP) == (0 if n <= 96 else 1)
+    c = AC.nms_case(n_glo, n_new, 1000 + 17 * n_glo + n_new, spread=2.0, n_centres=max(1, n // 3),
+                    scene_seed=2, max_extra=3)
+    corners, scores, init_id, cam_poses, fusion_list, valid_num = (
+        c[k] for k in ("corners", "scores", "init_id", "cam_poses", "fusion_list", "valid_num"))
     iou = L.obb_iou_matrix(_t(corners)).cpu().numpy()
     np.testing.assert_array_equal(iou, OR.obb_iou_matrix(corners))
     got = HipBackend(L).nms(iou, corners, scores, init_id, cam_poses, fusion_list, valid_num)
