@@ -17,13 +17,14 @@ import os
 import numpy as np
 import torch
 
+from . import _abi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # BF_LIB_PATH: a diagnostic build of the same sources (e.g. one that forces a rare kernel path)
 LIB_PATH = os.environ.get("BF_LIB_PATH") or os.path.join(HERE, "libboxfusion_hip.so")
 _LIB = None
 
-c_int, c_float, c_double, c_void_p, c_size_t = (ctypes.c_int, ctypes.c_float, ctypes.c_double,
-                                                ctypes.c_void_p, ctypes.c_size_t)
+c_float, c_void_p = ctypes.c_float, ctypes.c_void_p
 
 BF_DEV_FUSION_LIST_OVERFLOW = 1
 BF_DEV_HULL_OVERFLOW = 2
@@ -31,39 +32,9 @@ BF_DEV_VIEW_OVERFLOW = 4
 BF_DEV_INDEX_RANGE = 8
 BF_DEV_HULL_TRUNC = 16
 
-
-class NmsCfg(ctypes.Structure):
-    _fields_ = [("iou_threshold", c_double), ("translation_gap", c_float),
-                ("rotation_gap", c_float), ("center_gap", c_double),
-                ("max_list", c_int), ("list_capacity", c_int)]
-
-
-class CorrCfg(ctypes.Structure):
-    _fields_ = [("small_size", c_double), ("threshold", c_double),
-                ("translation_gap", c_float), ("rotation_gap", c_float),
-                ("W", c_float), ("H", c_float), ("max_list", c_int), ("list_capacity", c_int)]
-
-
-class FuseCfg(ctypes.Structure):
-    _fields_ = [("iters", c_int), ("pst_size", c_int), ("max_accept", c_int),
-                ("legacy_promotion", c_int),
-                ("center_init", c_double), ("shape_init", c_double),
-                ("center_coef", c_double), ("shape_coef", c_double),
-                ("beta", c_double), ("min_scale", c_double),
-                ("img_h", c_float), ("img_w", c_float), ("K", c_float * 16)]
-
-
-class FilterCfg(ctypes.Structure):
-    _fields_ = [("score_thresh", c_float), ("floor_ratio", c_float), ("floor_half", c_float),
-                ("size_max", c_float), ("gap_w", ctypes.c_int32), ("gap_h", ctypes.c_int32),
-                ("W", ctypes.c_int32), ("H", ctypes.c_int32), ("use_score", ctypes.c_int32),
-                ("use_uv", ctypes.c_int32), ("use_floor", ctypes.c_int32), ("use_large", ctypes.c_int32)]
-
-
-class RowsField(ctypes.Structure):
-    _fields_ = [("a", c_void_p), ("b", c_void_p), ("dst", c_void_p), ("n_a", ctypes.c_int64),
-                ("n_b", ctypes.c_int64), ("row_bytes", ctypes.c_int32), ("pad", ctypes.c_int32)]
-
+# the header's structs (all-zero GemmPlan = the product defaults)
+NmsCfg, CorrCfg, FuseCfg, FseqCfg, FilterCfg, RowsField, GemmPlan = map(_abi.struct, (
+    "bf_nms_cfg", "bf_corr_cfg", "bf_fuse_cfg", "bf_fseq_cfg", "bf_filter_cfg", "bf_rows_field", "bf_gemm_plan"))
 
 ROWS_MAX_FIELDS = 16
 
@@ -77,16 +48,9 @@ def lib():
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
             raise HipError(f"{LIB_PATH} is missing: build it with `python -m boxfusion_amd.build`")
-        _LIB = ctypes.CDLL(LIB_PATH)
-        _LIB.bf_version.restype = ctypes.c_char_p
-        _LIB.bf_obb_iou_workspace_size.restype = c_size_t
-        _LIB.bf_obb_iou_workspace_size.argtypes = [c_int]
-        _LIB.bf_depth_standardize_workspace_size.restype = c_size_t
-        _LIB.bf_depth_standardize_workspace_size.argtypes = [c_int, c_int, c_int]
-        for f in (_LIB.bf_png_workspace_bytes, _LIB.bf_zlib_workspace_bytes, _LIB.bf_png_rgb_workspace_bytes):
-            f.restype, f.argtypes = c_size_t, [c_int, c_int, c_int, ctypes.c_longlong]
-        _LIB.bf_jpeg_workspace_bytes.restype = c_size_t
-        _LIB.bf_jpeg_workspace_bytes.argtypes = [c_int, c_int, c_int]
+        # every entry point the header declares gets its argtypes and restype here, once: a call
+        # with the wrong number or kind of arguments raises instead of reading garbage
+        _LIB = _abi.declare(ctypes.CDLL(LIB_PATH))
     return _LIB
 
 
@@ -164,24 +128,23 @@ def box_corners(xyzlhw, R):
     R = _need(R.contiguous(), torch.float32, "R")
     n = xyzlhw.shape[0]
     out = torch.empty((n, 8, 3), dtype=torch.float32, device=xyzlhw.device)
-    _check(lib().bf_box_corners(_ptr(xyzlhw), _ptr(R), c_int(n), _ptr(out), _stream()),
-           "bf_box_corners")
+    _check(lib().bf_box_corners(_ptr(xyzlhw), _ptr(R), n, _ptr(out), _stream()), "bf_box_corners")
     return out
 
 
 def box_transform2world(xyzlhw, R, cam_pose):
     """in place on xyzlhw / R (both contiguous f32 device tensors)"""
     n = xyzlhw.shape[0]
-    _check(lib().bf_box_transform2world(_ptr(xyzlhw), _ptr(R), _ptr(cam_pose.contiguous()),
-                                        c_int(n), _stream()), "bf_box_transform2world")
+    _check(lib().bf_box_transform2world(_ptr(xyzlhw), _ptr(R), _ptr(cam_pose.contiguous()), n,
+                                        _stream()), "bf_box_transform2world")
 
 
 def project_boxes(corners, cam_pose, K, W, H):
     n = corners.shape[0]
     uv = torch.empty((n, 8, 2), dtype=torch.float32, device=corners.device)
     _check(lib().bf_project_boxes(_ptr(corners.contiguous()), _ptr(cam_pose.contiguous()),
-                                  _ptr(K.contiguous()), c_int(n), c_float(W), c_float(H), _ptr(uv),
-                                  _stream()), "bf_project_boxes")
+                                  _ptr(K.contiguous()), n, W, H, _ptr(uv), _stream()),
+           "bf_project_boxes")
     return uv
 
 
@@ -198,7 +161,7 @@ def obb_iou_matrix(corners):
     iou = torch.empty((n, n), dtype=torch.float64, device=corners.device)
     ws = torch.empty(max(1, int(lib().bf_obb_iou_workspace_size(n))), dtype=torch.uint8,
                      device=corners.device)
-    _check(lib().bf_obb_iou_matrix(_ptr(corners), c_int(n), _ptr(iou), _ptr(ws), _stream()),
+    _check(lib().bf_obb_iou_matrix(_ptr(corners), n, _ptr(iou), _ptr(ws), _stream()),
            "bf_obb_iou_matrix")
     return iou
 
@@ -270,9 +233,9 @@ def rows_gather(pairs, idx=None, n_out=None, outs=None, status=None):
         i32 = idx is not None and idx.dtype == torch.int32
         if status is None and idx is not None:
             status = status_word(outs[0].device)
-        _check(lib().bf_rows_gather(c_void_p(arr.ctypes.data), c_int(len(pairs)), _ptr(idx), c_int(int(i32)),
-                                    c_int(n_out), _ptr(status) if status is not None else None,
-                                    _stream()), "bf_rows_gather")
+        _check(lib().bf_rows_gather(arr.ctypes.data, len(pairs), _ptr(idx), int(i32), n_out,
+                                    _ptr(status) if status is not None else None, _stream()),
+               "bf_rows_gather")
     return outs
 
 
@@ -300,12 +263,10 @@ def nms_scan(iou, corners, scores, init_id, cam_poses, fl_items, fl_len, valid_n
         events = torch.empty((n + 1, 3), **i32)
         counts = torch.zeros(4, **i32)  # n_keep, n_success, n_events, status
     L = lib()
-    L.bf_nms_scan_workspace_size.restype = ctypes.c_size_t
-    ws = torch.empty(max(int(L.bf_nms_scan_workspace_size(c_int(n))), 8), dtype=torch.uint8, device=dev)
-    _check(L.bf_nms_scan_ws(_ptr(iou), _ptr(corners), _ptr(scores), _ptr(init_id),
-                            _ptr(cam_poses), c_int(n), _ptr(fl_items), _ptr(fl_len),
-                            _ptr(valid_num), _ptr(keep), _ptr(counts[0:1]), _ptr(succ),
-                            _ptr(counts[1:2]), _ptr(events), _ptr(counts[2:3]),
+    ws = torch.empty(max(L.bf_nms_scan_workspace_size(n), 8), dtype=torch.uint8, device=dev)
+    _check(L.bf_nms_scan_ws(_ptr(iou), _ptr(corners), _ptr(scores), _ptr(init_id), _ptr(cam_poses), n,
+                            _ptr(fl_items), _ptr(fl_len), _ptr(valid_num), _ptr(keep), _ptr(counts[0:1]),
+                            _ptr(succ), _ptr(counts[1:2]), _ptr(events), _ptr(counts[2:3]),
                             _ptr(counts[3:4]), ctypes.byref(cfg), _ptr(ws), _stream()), "bf_nms_scan_ws")
     return keep, succ, events, counts
 
@@ -314,7 +275,7 @@ def nms_scan_form(n, list_capacity, has_workspace=True):
     """the scan bf_nms_scan_ws launches (bf_nms_scan_form): 0 one wave on the IoU matrix, 1 one
     wave on the bit masks, 2 block scan with the IoU matrix in LDS, 3 block scan reading it from
     global memory; nms_scan always passes a workspace, bf_nms_scan none"""
-    return int(lib().bf_nms_scan_form(c_int(n), c_int(list_capacity), c_int(int(bool(has_workspace)))))
+    return int(lib().bf_nms_scan_form(n, list_capacity, int(bool(has_workspace))))
 
 
 def corr_assoc(corners, dims, scores, boxes2d, init_id, cam_poses, cur_pose, K, n_glo, mask,
@@ -331,12 +292,11 @@ def corr_assoc(corners, dims, scores, boxes2d, init_id, cam_poses, cur_pose, K, 
         counts = torch.zeros(3, **i32)  # n_keep, n_events, status
     succ = success if success.numel() else torch.zeros(1, **i32)
     _check(lib().bf_corr_assoc(_ptr(corners), _ptr(dims), _ptr(scores), _ptr(boxes2d),
-                               _ptr(init_id), _ptr(cam_poses), _ptr(cur_pose), _ptr(K),
-                               c_int(n_all), c_int(n_glo), _ptr(mask), c_int(mask.shape[0]),
-                               _ptr(succ), c_int(success.numel()), _ptr(fl_items), _ptr(fl_len),
-                               _ptr(valid_num), _ptr(keep), _ptr(counts[0:1]), _ptr(events),
-                               _ptr(counts[1:2]), _ptr(counts[2:3]), ctypes.byref(cfg),
-                               _stream()), "bf_corr_assoc")
+                               _ptr(init_id), _ptr(cam_poses), _ptr(cur_pose), _ptr(K), n_all,
+                               n_glo, _ptr(mask), mask.shape[0], _ptr(succ), success.numel(),
+                               _ptr(fl_items), _ptr(fl_len), _ptr(valid_num), _ptr(keep),
+                               _ptr(counts[0:1]), _ptr(events), _ptr(counts[1:2]),
+                               _ptr(counts[2:3]), ctypes.byref(cfg), _stream()), "bf_corr_assoc")
     return keep, events, counts
 
 
@@ -349,8 +309,8 @@ def corr_assoc_chained(corners, dims, scores, boxes2d, init_id, cam_poses, cur_p
     keep, events, counts = out
     _check(lib().bf_corr_assoc_chained(
         _ptr(corners), _ptr(dims), _ptr(scores), _ptr(boxes2d), _ptr(init_id), _ptr(cam_poses),
-        _ptr(cur_pose), _ptr(K), c_int(scores.shape[0]), c_int(n_glo), _ptr(mask), _ptr(n_mask),
-        _ptr(success), _ptr(n_success), _ptr(fl_items), _ptr(fl_len), _ptr(valid_num), _ptr(keep),
+        _ptr(cur_pose), _ptr(K), scores.shape[0], n_glo, _ptr(mask), _ptr(n_mask), _ptr(success),
+        _ptr(n_success), _ptr(fl_items), _ptr(fl_len), _ptr(valid_num), _ptr(keep),
         _ptr(counts[0:1]), _ptr(events), _ptr(counts[1:2]), _ptr(counts[2:3]), ctypes.byref(cfg),
         _stream()), "bf_corr_assoc_chained")
     return keep, events, counts
@@ -378,10 +338,9 @@ def fusion_fit(view_off, n_views, view_box, view_R, view_score, view_pose, view_
         max_views = int(n_views.max().item()) if n_views.numel() else 1
     max_views = max(1, min(int(max_views), 32))
     L = lib()
-    L.bf_fusion_fit_workspace_size.restype = ctypes.c_size_t
-    nbytes = L.bf_fusion_fit_workspace_size(c_int(n_jobs), c_int(max_views), c_int(cfg.pst_size))
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-    launch = lambda: _check(L.bf_fusion_fit(_ptr(view_off), _ptr(n_views), c_int(n_jobs), c_int(max_views),
+    nbytes = L.bf_fusion_fit_workspace_size(n_jobs, max_views, cfg.pst_size)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    launch = lambda: _check(L.bf_fusion_fit(_ptr(view_off), _ptr(n_views), n_jobs, max_views,
                                             _ptr(view_box), _ptr(view_R), _ptr(view_score), _ptr(view_pose),
                                             _ptr(view_tc), _ptr(pst), ctypes.byref(cfg), _ptr(out_box),
                                             _ptr(out_upd), _ptr(out_it), _ptr(tr), _ptr(status), _ptr(ws),
@@ -406,29 +365,23 @@ def fusion_writeback(out_box, updated, rows, target):
     _need(target, torch.float32, "target")
     if not target.is_contiguous():
         raise HipError("fusion_writeback: target must be contiguous")
-    _check(lib().bf_fusion_writeback(_ptr(out_box), _ptr(updated), _ptr(rows), c_int(rows.shape[0]),
-                                     _ptr(target), c_int(target.shape[1]), _stream()),
+    _check(lib().bf_fusion_writeback(_ptr(out_box), _ptr(updated), _ptr(rows), rows.shape[0],
+                                     _ptr(target), target.shape[1], _stream()),
            "bf_fusion_writeback")
 
 
 def fusion_fitness(box, R, view_pose, view_tc, pst, search_size, cfg: FuseCfg):
     nv = view_pose.shape[0]
     out = torch.empty(pst.shape[0], dtype=torch.float32, device=box.device)
-    _check(lib().bf_fusion_fitness(_ptr(box), _ptr(R), c_int(nv), _ptr(view_pose),
-                                   _ptr(view_tc), _ptr(pst), c_int(pst.shape[0]),
-                                   _ptr(search_size), ctypes.byref(cfg), _ptr(out), _stream()),
-           "bf_fusion_fitness")
+    _check(lib().bf_fusion_fitness(_ptr(box), _ptr(R), nv, _ptr(view_pose), _ptr(view_tc),
+                                   _ptr(pst), pst.shape[0], _ptr(search_size), ctypes.byref(cfg),
+                                   _ptr(out), _stream()), "bf_fusion_fitness")
     return out
 
 
 # ------------------------------------------------------------------------------------------
 # keyframe sequencer (bf_fseq_*)
 # ------------------------------------------------------------------------------------------
-class FseqCfg(ctypes.Structure):
-    _fields_ = [("nms", NmsCfg), ("corr", CorrCfg), ("fuse", FuseCfg), ("use_fusion", ctypes.c_int32),
-                ("strict_hull", ctypes.c_int32)]
-
-
 FSEQ_STATE_N = 16
 
 
@@ -438,14 +391,9 @@ class FusionSequencer:
     Calls launch on the calling thread's current stream."""
 
     def __init__(self):
-        L = lib()
-        L.bf_fseq_error.restype = ctypes.c_char_p
-        L.bf_fseq_error.argtypes = [c_void_p]
-        L.bf_fseq_destroy.restype = None
-        L.bf_fseq_destroy.argtypes = [c_void_p]
-        self._L = L
+        self._L = lib()
         self.h = c_void_p()
-        _check(L.bf_fseq_create(ctypes.byref(self.h)), "bf_fseq_create")
+        _check(self._L.bf_fseq_create(ctypes.byref(self.h)), "bf_fseq_create")
         self._state = np.zeros(FSEQ_STATE_N, np.int64)
         _LIVE_SEQUENCERS.add(self)
 
@@ -468,9 +416,8 @@ class FusionSequencer:
         sizes = np.ascontiguousarray(sizes, np.int32)
         p_rows = int(fields[0].shape[0])
         self._rc(self._L.bf_fseq_keyframes(
-            self.h, ctypes.byref(cfg), c_int(len(sizes)), sizes.ctypes.data_as(c_void_p),
-            ctypes.c_int64(int(p_base)), ctypes.c_int64(p_rows), *[_ptr(t) for t in fields], _ptr(K),
-            _ptr(pst), _stream()), "bf_fseq_keyframes")
+            self.h, ctypes.byref(cfg), len(sizes), sizes.ctypes.data_as(c_void_p), int(p_base),
+            p_rows, *[_ptr(t) for t in fields], _ptr(K), _ptr(pst), _stream()), "bf_fseq_keyframes")
 
     def sync(self):
         self._rc(self._L.bf_fseq_sync(self.h), "bf_fseq_sync")
@@ -483,7 +430,7 @@ class FusionSequencer:
     def lists(self, which, rows, items):
         lens = np.zeros(max(rows, 1), np.int32)
         flat = np.zeros(max(items, 1), np.int32)
-        self._rc(self._L.bf_fseq_lists(self.h, c_int(which), lens.ctypes.data_as(c_void_p),
+        self._rc(self._L.bf_fseq_lists(self.h, which, lens.ctypes.data_as(c_void_p),
                                        flat.ctypes.data_as(c_void_p)), "bf_fseq_lists")
         off = np.concatenate([[0], np.cumsum(lens[:rows])])
         fl = flat.tolist()
@@ -537,8 +484,8 @@ def detection_filter(scores, proj_xy, box3d, cfg: FilterCfg, with_bits=False):
     bits = torch.empty(scores.shape, dtype=torch.uint8, device=scores.device) if with_bits else None
     _check(lib().bf_detection_filter(_ptr(_need(scores.contiguous(), torch.float32, "scores")),
                                      _ptr(_need(proj_xy.contiguous(), torch.float32, "proj_xy")),
-                                     _ptr(_need(box3d.contiguous(), torch.float32, "box3d")),
-                                     c_int(n), ctypes.byref(cfg), _ptr(keep), _ptr(bits), _stream()),
+                                     _ptr(_need(box3d.contiguous(), torch.float32, "box3d")), n,
+                                     ctypes.byref(cfg), _ptr(keep), _ptr(bits), _stream()),
            "bf_detection_filter")
     return (keep.bool(), bits) if with_bits else keep.bool()
 
@@ -560,7 +507,7 @@ def depth_workspace(b, h, w, device):
     key = (dev.index, stream, b, h, w)
     ws = _DS_WS.get(key)
     if ws is None:
-        size = int(lib().bf_depth_standardize_workspace_size(c_int(b), c_int(h), c_int(w)))
+        size = int(lib().bf_depth_standardize_workspace_size(b, h, w))
         ws = torch.zeros(max(size, 1), dtype=torch.uint8, device=dev)
         _DS_WS[key] = ws
     return ws
@@ -597,9 +544,9 @@ def depth_preprocess(depth, K=None, RT=None, max_depth=10.0, out=None, params=No
                            "(new_depth_workspace): the per-stream cached workspace is shared")
         ws = depth_workspace(b, h, w, depth.device)
     launch = lambda: _check(lib().bf_depth_preprocess(
-        _ptr(depth), c_int(b), c_int(h), c_int(w), _ptr(out), _ptr(params), _ptr(K) if bp else None,
-        _ptr(RT) if bp else None, c_float(max_depth if max_depth is not None else 0.0),
-        _ptr(xyz) if bp else None, _ptr(valid) if bp else None, _ptr(ws), _stream()), "bf_depth_preprocess")
+        _ptr(depth), b, h, w, _ptr(out), _ptr(params), _ptr(K) if bp else None, _ptr(RT) if bp else None,
+        max_depth if max_depth is not None else 0.0, _ptr(xyz) if bp else None, _ptr(valid) if bp else None,
+        _ptr(ws), _stream()), "bf_depth_preprocess")
     # KernelTimer, by hand (not _timed): the outputs and the workspace above are allocated before
     # the start event, so the events bracket the launches only
     t = _timer()
@@ -621,9 +568,9 @@ def backproject(depth, K, RT, max_depth=10.0):
     xyz = torch.empty((h, w, 3), dtype=torch.float32, device=depth.device)
     valid = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
     _check(lib().bf_backproject(_ptr(depth.contiguous()), _ptr(K.contiguous()),
-                                _ptr(RT.contiguous()), c_int(h), c_int(w),
-                                c_float(max_depth if max_depth is not None else 0.0), _ptr(xyz),
-                                _ptr(valid), _stream()), "bf_backproject")
+                                _ptr(RT.contiguous()), h, w,
+                                max_depth if max_depth is not None else 0.0, _ptr(xyz), _ptr(valid),
+                                _stream()), "bf_backproject")
     return xyz, valid.bool()
 
 
@@ -631,13 +578,6 @@ def backproject(depth, K, RT, max_depth=10.0):
 # MFMA tower kernels
 # ------------------------------------------------------------------------------------------
 ACT = {None: 0, "none": 0, "gelu": 1, "relu": 2}
-
-
-class GemmPlan(ctypes.Structure):
-    """bf_gemm_plan: per-call GEMM options (include/boxfusion_hip.h); all-zero = product defaults"""
-    _fields_ = [("cu_budget", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("kernel", ctypes.c_int32),
-                ("variant", ctypes.c_int32), ("group_m", ctypes.c_int32), ("balanced", ctypes.c_int32),
-                ("objective", ctypes.c_int32)]
 
 
 # The CU budget a thread's GEMMs pass in their plan (0 = every CU).  Host-side, per thread: the C
@@ -682,7 +622,7 @@ def _plan(plan):
 def gemm_tile_rows(M, N, K, plan=None):
     """tile height the persistent bf16 GEMM takes for this shape under `plan` (as gemm()'s plan
     argument); host-only, needs no GPU"""
-    r = lib().bf_gemm_tile_rows_plan(c_int(M), c_int(N), c_int(K), _plan(plan))
+    r = lib().bf_gemm_tile_rows_plan(M, N, K, _plan(plan))
     if r <= 0:
         raise HipError(f"bf_gemm_tile_rows_plan failed with bf_status {r}")
     return r
@@ -690,7 +630,7 @@ def gemm_tile_rows(M, N, K, plan=None):
 
 def gemm_grid(M, N, K, plan=None):
     """workgroups of the persistent grid at that height (CU-time = this x the GEMM's duration)"""
-    r = lib().bf_gemm_grid_plan(c_int(M), c_int(N), c_int(K), _plan(plan))
+    r = lib().bf_gemm_grid_plan(M, N, K, _plan(plan))
     if r <= 0:
         raise HipError(f"bf_gemm_grid_plan failed with bf_status {r}")
     return r
@@ -702,7 +642,7 @@ def _gemm_work(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out
     N, K = w.shape
     ob = (out.dtype if out is not None else out_dtype) == torch.bfloat16
     tags = dict(kind="gemm", act=ACT[act], out_bf16=ob, resid=resid is not None, M=M, N=N, K=K,
-                large=bool(lib().bf_gemm_large_tiles(c_int(M), c_int(N), c_int(K))))
+                large=bool(lib().bf_gemm_large_tiles(M, N, K)))
     nbytes = 2.0 * (M * K + N * K) + M * N * (2 if ob else 4)
     if resid is not None:
         nbytes += 4.0 * (M * N if not resid_mod else resid_mod * N)
@@ -730,13 +670,13 @@ def gemm(a, w, bias=None, act=None, resid=None, resid_mod=0, out=None, out_dtype
         _need(bias, torch.float32, "bias")
     if a.stride(1) != 1 or w.stride(1) != 1 or out.stride(1) != 1:
         raise HipError("gemm operands need unit column stride")
-    _check(lib().bf_gemm_bf16_plan(c_void_p(a.data_ptr()), c_int(a.stride(0)), c_void_p(w.data_ptr()),
-                                   c_int(w.stride(0)), _ptr(bias) if bias is not None else None,
-                                   c_void_p(resid.data_ptr()) if resid is not None else None,
-                                   c_int(resid.stride(0) if resid is not None else 0), c_int(resid_mod),
-                                   c_void_p(out.data_ptr()), c_int(out.stride(0)), c_int(c_bf16),
-                                   _ptr(row_map) if row_map is not None else None, c_int(M), c_int(N),
-                                   c_int(K), c_int(ACT[act]), _plan(plan), _stream()), "bf_gemm_bf16")
+    _check(lib().bf_gemm_bf16_plan(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0),
+                                   _ptr(bias) if bias is not None else None,
+                                   resid.data_ptr() if resid is not None else None,
+                                   resid.stride(0) if resid is not None else 0, resid_mod,
+                                   out.data_ptr(), out.stride(0), c_bf16,
+                                   _ptr(row_map) if row_map is not None else None, M, N, K, ACT[act],
+                                   _plan(plan), _stream()), "bf_gemm_bf16")
     return out
 
 
@@ -763,14 +703,11 @@ def attention(q, k, v, o, batch, heads, sq, sk, head_dim, scale, q_bs=None, k_bs
         _need(o_map, torch.int32, "o_map")
         if o_map.numel() < batch * sq:
             raise HipError(f"o_map has {o_map.numel()} rows < batch*sq = {batch * sq}")
-    LL = ctypes.c_longlong
-    _check(lib().bf_attention_bf16_ex(c_void_p(q.data_ptr()), c_void_p(k.data_ptr()),
-                                      c_void_p(v.data_ptr()), c_void_p(o.data_ptr()), c_int(batch),
-                                      c_int(heads), c_int(sq), c_int(sk), c_int(head_dim),
-                                      c_int(q.stride(0)), c_int(k.stride(0)), c_int(v.stride(0)),
-                                      c_int(o.stride(0)), LL(q_bs), LL(k_bs), LL(v_bs), LL(o_bs),
-                                      c_float(scale), _ptr(o_map) if o_map is not None else None,
-                                      c_int(variant or _knobs().get("attn_variant", 0)), _stream()),
+    _check(lib().bf_attention_bf16_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), batch,
+                                      heads, sq, sk, head_dim, q.stride(0), k.stride(0),
+                                      v.stride(0), o.stride(0), q_bs, k_bs, v_bs, o_bs, scale,
+                                      _ptr(o_map) if o_map is not None else None,
+                                      variant or _knobs().get("attn_variant", 0), _stream()),
            "bf_attention_bf16_ex")
     return o
 
@@ -793,13 +730,10 @@ def attention_fp8out(q, k, v, o, batch, heads, sq, sk, head_dim, scale, out_qsca
     k_bs = sk * k.stride(0) if k_bs is None else k_bs
     v_bs = sk * v.stride(0) if v_bs is None else v_bs
     o_bs = sq * o.stride(0) if o_bs is None else o_bs
-    LL = ctypes.c_longlong
-    _check(lib().bf_attention_fp8out_ex(c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
-                                        c_void_p(o.data_ptr()), c_int(batch), c_int(heads), c_int(sq),
-                                        c_int(sk), c_int(head_dim), c_int(q.stride(0)), c_int(k.stride(0)),
-                                        c_int(v.stride(0)), c_int(o.stride(0)), LL(q_bs), LL(k_bs), LL(v_bs),
-                                        LL(o_bs), c_float(scale), c_float(out_qscale),
-                                        c_int(variant or _knobs().get("attn_variant", 0)), _stream()),
+    _check(lib().bf_attention_fp8out_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), batch, heads,
+                                        sq, sk, head_dim, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+                                        q_bs, k_bs, v_bs, o_bs, scale, out_qscale,
+                                        variant or _knobs().get("attn_variant", 0), _stream()),
            "bf_attention_fp8out_ex")
     return o
 
@@ -813,11 +747,10 @@ def layernorm(x, weight, bias, eps, out=None, row_map=None, out_dtype=torch.bflo
         out = torch.empty((M, C), dtype=out_dtype, device=x.device)
     if out.dtype not in (torch.bfloat16, torch.float32) or x.stride(1) != 1 or out.stride(1) != 1:
         raise HipError("layernorm: f32 in, bf16 / f32 out, unit column stride")
-    _check(lib().bf_layernorm_out(c_void_p(x.data_ptr()), c_int(x.stride(0)), _ptr(weight),
-                                  _ptr(bias), c_float(eps), c_void_p(out.data_ptr()),
-                                  c_int(out.stride(0)), c_int(int(out.dtype == torch.float32)),
-                                  _ptr(row_map) if row_map is not None else None, c_int(M), c_int(C),
-                                  _stream()), "bf_layernorm_out")
+    _check(lib().bf_layernorm_out(x.data_ptr(), x.stride(0), _ptr(weight), _ptr(bias), eps,
+                                  out.data_ptr(), out.stride(0), int(out.dtype == torch.float32),
+                                  _ptr(row_map) if row_map is not None else None, M, C, _stream()),
+           "bf_layernorm_out")
     return out
 
 
@@ -826,13 +759,10 @@ def attention_causal(q, k, v, o, batch, heads, s, head_dim, scale):
     """causal self-attention (CLIP text tower): q/k/v/o token-major 2-D views [batch*s, >= heads*D]"""
     for x, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
         _need(x, torch.bfloat16, n)
-    LL = ctypes.c_longlong
-    _check(lib().bf_attention_causal(c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
-                                     c_void_p(o.data_ptr()), c_int(batch), c_int(heads), c_int(s),
-                                     c_int(head_dim), c_int(q.stride(0)), c_int(k.stride(0)),
-                                     c_int(v.stride(0)), c_int(o.stride(0)), LL(s * q.stride(0)),
-                                     LL(s * k.stride(0)), LL(s * v.stride(0)), LL(s * o.stride(0)),
-                                     c_float(scale), _stream()), "bf_attention_causal")
+    _check(lib().bf_attention_causal(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), batch, heads,
+                                     s, head_dim, q.stride(0), k.stride(0), v.stride(0), o.stride(0),
+                                     s * q.stride(0), s * k.stride(0), s * v.stride(0), s * o.stride(0),
+                                     scale, _stream()), "bf_attention_causal")
     return o
 
 
@@ -851,8 +781,8 @@ def token_embed(ids, table, pos, out=None, status=None):
     own = status is None
     if own:
         status = torch.zeros(1, dtype=torch.int32, device=ids.device)
-    _check(lib().bf_token_embed(_ptr(ids), c_int(N * S), _ptr(table), c_int(table.shape[0]), _ptr(pos),
-                                c_int(S), c_int(W), _ptr(out), _ptr(status), _stream()), "bf_token_embed")
+    _check(lib().bf_token_embed(_ptr(ids), N * S, _ptr(table), table.shape[0], _ptr(pos), S, W, _ptr(out),
+                                _ptr(status), _stream()), "bf_token_embed")
     if own and int(status.item()) & BF_DEV_INDEX_RANGE:
         raise HipError("bf_token_embed: a token id outside the vocabulary (BF_DEV_INDEX_RANGE)")
     return out
@@ -867,8 +797,7 @@ def text_pool(ids, x, out=None):
     if out is None:
         out = torch.empty((N, W), dtype=torch.float32, device=x.device)
     _need(out, torch.float32, "out")
-    _check(lib().bf_text_pool(_ptr(ids), c_int(N), c_int(S), _ptr(x), c_int(W), _ptr(out), _stream()),
-           "bf_text_pool")
+    _check(lib().bf_text_pool(_ptr(ids), N, S, _ptr(x), W, _ptr(out), _stream()), "bf_text_pool")
     return out
 
 
@@ -878,7 +807,7 @@ def l2_normalize_rows(x, out=None):
     if out is None:
         out = torch.empty_like(x)
     _need(out, torch.float32, "out")
-    _check(lib().bf_l2_normalize_rows(_ptr(x), c_int(x.shape[0]), c_int(x.shape[1]), _ptr(out), _stream()),
+    _check(lib().bf_l2_normalize_rows(_ptr(x), x.shape[0], x.shape[1], _ptr(out), _stream()),
            "bf_l2_normalize_rows")
     return out
 
@@ -910,9 +839,8 @@ def ingest_rgbd(bgr, depth_u16, depth_scale, rot_k=0, rgb_out=None, depth_out=No
     _need(rgb_out, torch.uint8, "rgb_out")
     if depth_u16 is not None and depth_out is None:
         depth_out = torch.empty((F_, Ho, Wo), dtype=torch.float32, device=bgr.device)
-    _check(lib().bf_ingest_rgbd(_ptr(bgr), c_int(Hc), c_int(Wc), _ptr(depth_u16), c_int(Hd), c_int(Wd),
-                                c_int(F_), c_float(depth_scale), c_int(k), c_int(int(bool(src_bgr))), _ptr(rgb_out),
-                                _ptr(depth_out) if depth_u16 is not None else None, _stream()),
+    _check(lib().bf_ingest_rgbd(_ptr(bgr), Hc, Wc, _ptr(depth_u16), Hd, Wd, F_, depth_scale, k, int(bool(src_bgr)),
+                                _ptr(rgb_out), _ptr(depth_out) if depth_u16 is not None else None, _stream()),
            "bf_ingest_rgbd")
     return rgb_out, depth_out
 
@@ -956,8 +884,8 @@ def _decode_batch(name, entry, workspace_bytes, status_bits, noun, data, offsets
     wb = workspace_bytes(F_, H, W, *sizes[:1])
     if work is None or work.numel() < wb:
         work = torch.empty(max(wb, 1), dtype=torch.uint8, device=data.device)
-    _check(entry(_ptr(data), _ptr(offsets), c_int(F_), c_int(H), c_int(W), *map(ctypes.c_longlong, sizes), *extra,
-                 _ptr(out), _ptr(work), c_size_t(wb), _ptr(status), _stream()), entry.__name__)
+    _check(entry(_ptr(data), _ptr(offsets), F_, H, W, *sizes, *extra, _ptr(out), _ptr(work), wb, _ptr(status),
+                 _stream()), entry.__name__)
     if check:
         st = status.cpu()
         bad = torch.nonzero(st).flatten().tolist()
@@ -977,7 +905,7 @@ def png_decode_u16(files, offsets, H, W, out=None, offsets_host=None, check=True
     that did not decode."""
     L = lib()
     entry, dt, extra = ((L.bf_png_decode_u16, torch.uint16, ()) if depth_scale is None else
-                        (L.bf_png_decode_depth, torch.float32, (c_float(depth_scale),)))
+                        (L.bf_png_decode_depth, torch.float32, (depth_scale,)))
     return _decode_batch("png_decode_u16", entry, png_workspace_bytes, PNG_STATUS, "file", files, offsets, H, W, (),
                          dt, out, offsets_host, check, work, extra)
 
@@ -999,7 +927,7 @@ def zlib_decode_u16(streams, offsets, H, W, out=None, offsets_host=None, check=T
     (bf_zlib_decode_depth).  check=True synchronises and raises on any stream that did not decode."""
     L = lib()
     entry, dt, extra = ((L.bf_zlib_decode_u16, torch.uint16, ()) if depth_scale is None else
-                        (L.bf_zlib_decode_depth, torch.float32, (c_float(depth_scale),)))
+                        (L.bf_zlib_decode_depth, torch.float32, (depth_scale,)))
     return _decode_batch("zlib_decode_u16", entry, zlib_workspace_bytes, ZLIB_STATUS, "stream", streams, offsets, H, W,
                          (), dt, out, offsets_host, check, work, extra)
 
@@ -1052,8 +980,8 @@ def cv2_resize_u8(src, Wd, Hd, out=None):
     F_, Hs, Ws, cn = x.shape
     if out is None:
         out = torch.empty((F_, Hd, Wd, cn), dtype=torch.uint8, device=src.device)
-    _check(lib().bf_cv2_resize_u8(_ptr(x), c_int(Hs), c_int(Ws), c_int(cn), c_int(Hd), c_int(Wd), c_int(F_),
-                                  _ptr(out), _stream()), "bf_cv2_resize_u8")
+    _check(lib().bf_cv2_resize_u8(_ptr(x), Hs, Ws, cn, Hd, Wd, F_, _ptr(out), _stream()),
+           "bf_cv2_resize_u8")
     if src.dim() == 2:
         return out[0, :, :, 0]
     return out[0] if src.dim() == 3 else out
@@ -1145,17 +1073,15 @@ def resize_bicubic_u8(src, Hd, Wd, out=None):
     by, ky = _bicubic_tables(Hs, Hd, x.device) if Hs != Hd else (None, None)
     tmp = (torch.empty((F_, Hs, Wd, 3), dtype=torch.uint8, device=x.device)
            if Ws != Wd and Hs != Hd else None)
-    _check(lib().bf_resize_bicubic_u8(_ptr(x), c_int(F_), c_int(Hs), c_int(Ws), c_int(Hd), c_int(Wd), _ptr(kx),
-                                      _ptr(bx), c_int(kx.shape[1] if kx is not None else 0), _ptr(ky), _ptr(by),
-                                      c_int(ky.shape[1] if ky is not None else 0), _ptr(tmp), _ptr(out),
-                                      _stream()), "bf_resize_bicubic_u8")
+    _check(lib().bf_resize_bicubic_u8(_ptr(x), F_, Hs, Ws, Hd, Wd, _ptr(kx), _ptr(bx),
+                                      kx.shape[1] if kx is not None else 0, _ptr(ky), _ptr(by),
+                                      ky.shape[1] if ky is not None else 0, _ptr(tmp), _ptr(out), _stream()),
+           "bf_resize_bicubic_u8")
     return out[0] if src.dim() == 3 else out
 
 
 def _cloud_blocks(items, groups):
-    L = lib()
-    L.bf_cloud_blocks.restype, L.bf_cloud_blocks.argtypes = c_size_t, [ctypes.c_longlong, c_int]
-    return max(int(L.bf_cloud_blocks(int(items), int(groups))), 1)
+    return max(lib().bf_cloud_blocks(int(items), int(groups)), 1)
 
 
 def _cloud_inputs(name, xyz, valid, rgb):
@@ -1187,8 +1113,8 @@ def cloud_pack(xyz, valid, rgb):
     out = torch.empty((B * H * W, 6), dtype=torch.float32, device=xyz.device)
     offsets = torch.empty(B + 1, dtype=torch.int32, device=xyz.device)
     work = torch.empty(_cloud_blocks(H * W, B), dtype=torch.int32, device=xyz.device)
-    _check(lib().bf_cloud_pack(_ptr(xyz), _ptr(valid), _ptr(rgb), c_int(B), c_int(H), c_int(W), _ptr(out),
-                               _ptr(offsets), _ptr(work), _stream()), "bf_cloud_pack")
+    _check(lib().bf_cloud_pack(_ptr(xyz), _ptr(valid), _ptr(rgb), B, H, W, _ptr(out), _ptr(offsets),
+                               _ptr(work), _stream()), "bf_cloud_pack")
     return out, offsets
 
 
@@ -1227,9 +1153,8 @@ def cloud_integrate(xyz, valid, rgb, fine_step, table, stats, merge=True):
     _need(stats, torch.int64, "cloud_integrate: stats")
     if table.dim() != 2 or table.shape[1] != CLOUD_SLOT_WORDS or stats.numel() < 8:
         raise HipError("cloud_integrate: table [capacity,5] / stats [8] of cloud_table")
-    _check(lib().bf_cloud_integrate(_ptr(xyz), _ptr(valid), _ptr(rgb), ctypes.c_longlong(n), c_float(float(fine_step)),
-                                    _ptr(table), ctypes.c_longlong(table.shape[0]), _ptr(stats),
-                                    c_int(int(bool(merge))), _stream()), "bf_cloud_integrate")
+    _check(lib().bf_cloud_integrate(_ptr(xyz), _ptr(valid), _ptr(rgb), n, fine_step, _ptr(table), table.shape[0],
+                                    _ptr(stats), int(bool(merge)), _stream()), "bf_cloud_integrate")
 
 
 def _cloud_extract_work(table):
@@ -1248,8 +1173,8 @@ def cloud_extract(table):
     sums = torch.empty((cap, 6), dtype=torch.int32, device=dev)
     n = torch.empty(1, dtype=torch.int32, device=dev)
     work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
-    _check(lib().bf_cloud_extract(_ptr(table), ctypes.c_longlong(cap), _ptr(key), _ptr(count), _ptr(sums), _ptr(n),
-                                  _ptr(work), _stream()), "bf_cloud_extract")
+    _check(lib().bf_cloud_extract(_ptr(table), cap, _ptr(key), _ptr(count), _ptr(sums), _ptr(n), _ptr(work),
+                                  _stream()), "bf_cloud_extract")
     return key, count, sums, n
 
 
@@ -1299,10 +1224,6 @@ def _tsdf_arrays(name, keys, touched, vox=None, stats=None):
     return cap
 
 
-def _intr4(intr):
-    return [c_float(float(np.float32(v))) for v in intr]
-
-
 def _tsdf_touch_work(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, stats):
     n = float(depth.numel())
     return dict(kind="tsdf_touch", n=int(n)), 0.0, n * 4
@@ -1315,9 +1236,8 @@ def tsdf_touch(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched
     depth, poses, _ = _tsdf_frames("tsdf_touch", depth, poses)
     cap = _tsdf_arrays("tsdf_touch", keys, touched, stats=stats)
     B, H, W = depth.shape
-    _check(lib().bf_tsdf_touch(_ptr(depth), _ptr(poses), c_int(B), c_int(H), c_int(W), *_intr4(intr),
-                               c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(max_depth)), _ptr(keys),
-                               _ptr(touched), ctypes.c_longlong(cap), _ptr(stats), _stream()), "bf_tsdf_touch")
+    _check(lib().bf_tsdf_touch(_ptr(depth), _ptr(poses), B, H, W, *intr, voxel, int(trunc_voxels), max_depth,
+                               _ptr(keys), _ptr(touched), cap, _ptr(stats), _stream()), "bf_tsdf_touch")
 
 
 def _tsdf_update_work(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touched, vox, stats, rgb=None,
@@ -1339,10 +1259,9 @@ def tsdf_update(depth, poses, intr, voxel, trunc_voxels, max_depth, keys, touche
     slots = torch.empty(cap, dtype=torch.int32, device=dev)
     n = torch.empty(1, dtype=torch.int32, device=dev)
     work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
-    _check(lib().bf_tsdf_update(_ptr(depth), _ptr(rgb), _ptr(poses), c_int(B), c_int(H), c_int(W), *_intr4(intr),
-                                c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(max_depth)),
-                                c_int(int(max_weight)), _ptr(keys), _ptr(touched), _ptr(vox), ctypes.c_longlong(cap),
-                                _ptr(slots), _ptr(n), _ptr(work), _ptr(stats), _stream()), "bf_tsdf_update")
+    _check(lib().bf_tsdf_update(_ptr(depth), _ptr(rgb), _ptr(poses), B, H, W, *intr, voxel,
+                                int(trunc_voxels), max_depth, int(max_weight), _ptr(keys), _ptr(touched), _ptr(vox),
+                                cap, _ptr(slots), _ptr(n), _ptr(work), _ptr(stats), _stream()), "bf_tsdf_update")
 
 
 def _tsdf_extract_work(keys):
@@ -1359,8 +1278,8 @@ def tsdf_extract(keys):
     slot = torch.empty(cap, dtype=torch.int32, device=dev)
     n = torch.empty(1, dtype=torch.int32, device=dev)
     work = torch.empty(_cloud_blocks(cap, 1), dtype=torch.int32, device=dev)
-    _check(lib().bf_tsdf_extract(_ptr(keys), ctypes.c_longlong(cap), _ptr(key), _ptr(slot), _ptr(n), _ptr(work),
-                                 _stream()), "bf_tsdf_extract")
+    _check(lib().bf_tsdf_extract(_ptr(keys), cap, _ptr(key), _ptr(slot), _ptr(n), _ptr(work), _stream()),
+           "bf_tsdf_extract")
     return key, slot, n
 
 
@@ -1390,8 +1309,8 @@ def tsdf_surface(keys, vox, skey, sslot, voxel):
     vprefix = torch.empty(n, dtype=torch.int32, device=dev)
     fprefix = torch.empty(n, dtype=torch.int32, device=dev)
     totals = torch.empty(2, dtype=torch.int32, device=dev)
-    head = (_ptr(keys), ctypes.c_longlong(cap), _ptr(vox), _ptr(skey), _ptr(sslot), c_int(n), _ptr(rank), _ptr(bitmap),
-            _ptr(eflags), _ptr(vprefix), _ptr(fprefix))
+    head = (_ptr(keys), cap, _ptr(vox), _ptr(skey), _ptr(sslot), n, _ptr(rank), _ptr(bitmap), _ptr(eflags),
+            _ptr(vprefix), _ptr(fprefix))
     _check(lib().bf_tsdf_surface_count(*head, _ptr(totals), _stream()), "bf_tsdf_surface_count")
     nv, nq = totals.cpu().tolist()
     if nv == 0:
@@ -1399,7 +1318,7 @@ def tsdf_surface(keys, vox, skey, sslot, voxel):
     verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     vrgb = torch.empty((nv, 3), dtype=torch.uint8, device=dev)
     faces = torch.empty((max(2 * nq, 1), 3), dtype=torch.int32, device=dev)
-    _check(lib().bf_tsdf_surface_write(*head, c_float(float(voxel)), _ptr(verts), _ptr(vrgb), _ptr(faces), _stream()),
+    _check(lib().bf_tsdf_surface_write(*head, voxel, _ptr(verts), _ptr(vrgb), _ptr(faces), _stream()),
            "bf_tsdf_surface_write")
     return verts, vrgb, faces[:2 * nq]
 
@@ -1433,9 +1352,8 @@ def tsdf_raycast(keys, vox, poses, intr, H, W, voxel, trunc_voxels, near, far, m
     vertex = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
     normal = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
     rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=dev) if colour else None
-    _check(lib().bf_tsdf_raycast(_ptr(keys), _ptr(vox), ctypes.c_longlong(cap), _ptr(poses), c_int(V), c_int(H), c_int(W),
-                                 *_intr4(intr), c_float(float(voxel)), c_int(int(trunc_voxels)), c_float(float(near)),
-                                 c_float(float(far)), c_int(int(min_weight)), c_int(int(max_steps)), _ptr(depth),
+    _check(lib().bf_tsdf_raycast(_ptr(keys), _ptr(vox), cap, _ptr(poses), V, H, W, *intr, voxel,
+                                 int(trunc_voxels), near, far, int(min_weight), int(max_steps), _ptr(depth),
                                  _ptr(vertex), _ptr(normal), _ptr(rgb), _ptr(counters), _stream()), "bf_tsdf_raycast")
     return depth, vertex, normal, rgb
 
@@ -1457,19 +1375,38 @@ def depth_vertex_normal(depth, intr, max_depth, jump):
     H, W = depth.shape
     vertex = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
     normal = torch.empty((H, W, 3), dtype=torch.float32, device=depth.device)
-    _check(lib().bf_depth_vertex_normal(_ptr(depth), c_int(H), c_int(W), *_intr4(intr), c_float(float(max_depth)),
-                                        c_float(float(jump)), _ptr(vertex), _ptr(normal), _stream()),
-           "bf_depth_vertex_normal")
+    _check(lib().bf_depth_vertex_normal(_ptr(depth), H, W, *intr, max_depth, jump, _ptr(vertex),
+                                        _ptr(normal), _stream()), "bf_depth_vertex_normal")
     return vertex, normal
 
 
 def icp_blocks(H, W, stride):
     """rows of bf_icp_reduce's partials for a live map of H x W sampled at `stride`"""
-    lib().bf_icp_blocks.restype = c_int
-    n = int(lib().bf_icp_blocks(c_int(int(H)), c_int(int(W)), c_int(int(stride))))
+    n = lib().bf_icp_blocks(int(H), int(W), int(stride))
     if n <= 0:
         raise HipError(f"icp_blocks: H, W, stride = {H}, {W}, {stride}")
     return n
+
+
+def _reduce_setup(name, live_vertex, stride, T, w2c, w2c_name, intr, out):
+    """what icp_reduce and photo_reduce share: (stride, T and w2c as host f64 [12], the pinhole, the
+    partials workspace, out f64 [32] checked or allocated).  The pinhole is rounded to f32 and then
+    passed as doubles: the kernels' bits depend on it"""
+    stride = int(stride)
+    if stride < 1:
+        raise HipError(f"{name}: stride >= 1")
+    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
+    M = np.ascontiguousarray(np.asarray(w2c, np.float64).reshape(-1)[:12])
+    if T.size != 12 or M.size != 12:
+        raise HipError(f"{name}: T and {w2c_name} f64 [3,4]")
+    H, W = live_vertex.shape[:2]
+    dev = live_vertex.device
+    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty(32, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != 32:
+        raise HipError(f"{name}: out f64 [32]")
+    return stride, T, M, [float(np.float32(v)) for v in intr], partials, out
 
 
 def _icp_reduce_work(live_vertex, live_normal, stride, T, model_vertex, model_normal, model_w2c, intr, dist_max, cos_min,
@@ -1492,27 +1429,13 @@ def icp_reduce(live_vertex, live_normal, stride, T, model_vertex, model_normal, 
             raise HipError(f"icp_reduce: {name} [H,W,3], got {tuple(t.shape)}")
     if live_vertex.shape != live_normal.shape or model_vertex.shape != model_normal.shape:
         raise HipError("icp_reduce: a vertex and a normal map of one size each")
-    stride = int(stride)
-    if stride < 1:
-        raise HipError("icp_reduce: stride >= 1")
-    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
-    M = np.ascontiguousarray(np.asarray(model_w2c, np.float64).reshape(-1)[:12])
-    if T.size != 12 or M.size != 12:
-        raise HipError("icp_reduce: T and model_w2c f64 [3,4]")
+    stride, T, M, intr, partials, out = _reduce_setup("icp_reduce", live_vertex, stride, T, model_w2c, "model_w2c",
+                                                      intr, out)
     H, W = live_vertex.shape[:2]
     Hm, Wm = model_vertex.shape[:2]
-    dev = live_vertex.device
-    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
-    if out is None:
-        out = torch.empty(32, dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or out.numel() != 32:
-        raise HipError("icp_reduce: out f64 [32]")
-    dp = ctypes.POINTER(c_double)
-    fx, fy, cx, cy = (c_double(float(np.float32(v))) for v in intr)
-    _check(lib().bf_icp_reduce(_ptr(live_vertex.contiguous()), _ptr(live_normal.contiguous()), c_int(H), c_int(W),
-                               c_int(stride), T.ctypes.data_as(dp), _ptr(model_vertex.contiguous()),
-                               _ptr(model_normal.contiguous()), c_int(Hm), c_int(Wm), M.ctypes.data_as(dp), fx, fy, cx, cy,
-                               c_double(float(dist_max)), c_double(float(cos_min)), _ptr(partials), _ptr(out), _stream()),
+    _check(lib().bf_icp_reduce(_ptr(live_vertex.contiguous()), _ptr(live_normal.contiguous()), H, W, stride,
+                               T.ctypes.data, _ptr(model_vertex.contiguous()), _ptr(model_normal.contiguous()), Hm, Wm,
+                               M.ctypes.data, *intr, dist_max, cos_min, _ptr(partials), _ptr(out), _stream()),
            "bf_icp_reduce")
     return out
 
@@ -1535,7 +1458,7 @@ def grey_u8(rgb, out=None):
         out = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
     elif out.dtype != torch.float32 or out.numel() != B * H * W or not out.is_contiguous():
         raise HipError("grey_u8: out f32 [B,H,W]")
-    _check(lib().bf_grey_u8(_ptr(x), c_int(B), c_int(H), c_int(W), _ptr(out), _stream()), "bf_grey_u8")
+    _check(lib().bf_grey_u8(_ptr(x), B, H, W, _ptr(out), _stream()), "bf_grey_u8")
     out = out.view(B, H, W)
     return out[0] if rgb.dim() == 3 else out
 
@@ -1562,28 +1485,14 @@ def photo_reduce(live_vertex, live_intensity, stride, T, ref_intensity, ref_dept
             raise HipError(f"photo_reduce: {name} [H,W], got {tuple(t.shape)}")
     if live_intensity.shape != live_vertex.shape[:2] or ref_intensity.shape != ref_depth.shape:
         raise HipError("photo_reduce: an intensity map of the vertex map's size, and of the reference depth's")
-    stride = int(stride)
-    if stride < 1:
-        raise HipError("photo_reduce: stride >= 1")
-    T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1)[:12])
-    M = np.ascontiguousarray(np.asarray(ref_w2c, np.float64).reshape(-1)[:12])
-    if T.size != 12 or M.size != 12:
-        raise HipError("photo_reduce: T and ref_w2c f64 [3,4]")
+    stride, T, M, intr, partials, out = _reduce_setup("photo_reduce", live_vertex, stride, T, ref_w2c, "ref_w2c", intr,
+                                                      out)
     H, W = live_vertex.shape[:2]
     Hr, Wr = ref_intensity.shape
-    dev = live_vertex.device
-    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
-    if out is None:
-        out = torch.empty(32, dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or out.numel() != 32:
-        raise HipError("photo_reduce: out f64 [32]")
-    dp = ctypes.POINTER(c_double)
-    fx, fy, cx, cy = (c_double(float(np.float32(v))) for v in intr)
-    _check(lib().bf_photo_reduce(_ptr(live_vertex.contiguous()), _ptr(live_intensity.contiguous()), c_int(H), c_int(W),
-                                 c_int(stride), T.ctypes.data_as(dp), _ptr(ref_intensity.contiguous()),
-                                 _ptr(ref_depth.contiguous()), c_int(Hr), c_int(Wr), M.ctypes.data_as(dp), fx, fy, cx, cy,
-                                 c_double(float(dist_max)), c_double(float(intensity_max)), _ptr(partials), _ptr(out),
-                                 _stream()), "bf_photo_reduce")
+    _check(lib().bf_photo_reduce(_ptr(live_vertex.contiguous()), _ptr(live_intensity.contiguous()), H, W, stride,
+                                 T.ctypes.data, _ptr(ref_intensity.contiguous()), _ptr(ref_depth.contiguous()), Hr, Wr,
+                                 M.ctypes.data, *intr, dist_max, intensity_max, _ptr(partials), _ptr(out), _stream()),
+           "bf_photo_reduce")
     return out
 
 
@@ -1600,7 +1509,7 @@ def fern_upload(table, cells, device):
     t = np.ascontiguousarray(np.asarray(table, np.int32))
     if t.ndim != 2 or t.shape[1] != 5:
         raise HipError(f"fern_upload: table i32 [F,5], got {t.shape}")
-    _check(lib().bf_fern_table_check(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c_int(t.shape[0]), c_int(int(cells))),
+    _check(lib().bf_fern_table_check(t.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), t.shape[0], int(cells)),
            "bf_fern_table_check")
     return h2d(t, device)
 
@@ -1641,8 +1550,8 @@ def fern_encode(depth, rgb, cell, max_depth, ferns, with_means=False, codes=None
     means = None
     if with_means:
         means = torch.empty((B, max(H // cell, 0) * max(W // cell, 0) if cell > 0 else 0, 4), dtype=torch.int32, device=d.device)
-    _check(lib().bf_fern_encode(_ptr(d), _ptr(rgb), c_int(B), c_int(H), c_int(W), c_int(cell), c_float(float(max_depth)),
-                                _ptr(ferns.contiguous()), c_int(F), _ptr(means), _ptr(codes), _stream()), "bf_fern_encode")
+    _check(lib().bf_fern_encode(_ptr(d), _ptr(rgb), B, H, W, cell, max_depth, _ptr(ferns.contiguous()), F, _ptr(means),
+                                _ptr(codes), _stream()), "bf_fern_encode")
     return (codes, means) if with_means else codes
 
 
@@ -1666,17 +1575,15 @@ def fern_search(table, n, n_upper, queries, k, with_rows=False, top=None):
         raise HipError("fern_search: table, n and queries on one device")
     capacity, words = table.shape
     Q, k, n_upper = int(queries.shape[0]), int(k), int(n_upper)
-    lib().bf_fern_search_blocks.restype = c_int
-    blocks = int(lib().bf_fern_search_blocks(c_int(n_upper)))
+    blocks = lib().bf_fern_search_blocks(n_upper)
     part = torch.empty((max(Q, 1), max(blocks, 1), max(k, 1)), dtype=torch.int64, device=table.device)
     if top is None:
         top = torch.empty((Q, max(k, 1), 2), dtype=torch.int32, device=table.device)
     elif top.dtype != torch.int32 or top.numel() != Q * k * 2 or not top.is_contiguous():
         raise HipError("fern_search: top int32 [Q,k,2]")
     rows = torch.empty((Q, max(n_upper, 1)), dtype=torch.int32, device=table.device) if with_rows else None
-    _check(lib().bf_fern_search(_ptr(table), c_int(capacity), c_int(words * 8), _ptr(n), c_int(n_upper),
-                                _ptr(queries.contiguous()), c_int(Q), c_int(k), _ptr(part), _ptr(top), _ptr(rows), _stream()),
-           "bf_fern_search")
+    _check(lib().bf_fern_search(_ptr(table), capacity, words * 8, _ptr(n), n_upper, _ptr(queries.contiguous()), Q, k,
+                                _ptr(part), _ptr(top), _ptr(rows), _stream()), "bf_fern_search")
     return (top, rows) if with_rows else top
 
 
@@ -1703,9 +1610,9 @@ def fern_append(table, n, code, best, threshold, pose, frame, poses, ids, counte
     P = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(-1))
     if P.size != 16:
         raise HipError("fern_append: pose f32 [4,4]")
-    _check(lib().bf_fern_append(_ptr(table), c_int(capacity), c_int(words * 8), _ptr(n), _ptr(code), _ptr(best),
-                                c_int(int(threshold)), P.ctypes.data_as(ctypes.POINTER(c_float)), c_int(int(frame)), _ptr(poses),
-                                _ptr(ids), _ptr(counters), _stream()), "bf_fern_append")
+    _check(lib().bf_fern_append(_ptr(table), capacity, words * 8, _ptr(n), _ptr(code), _ptr(best), int(threshold),
+                                P.ctypes.data_as(ctypes.POINTER(c_float)), int(frame), _ptr(poses), _ptr(ids),
+                                _ptr(counters), _stream()), "bf_fern_append")
 
 
 # ------------------------------------------------------------------------------------------
@@ -1723,14 +1630,13 @@ def _render_cams(name, cams, V, intr):
     cams = _need(cams, torch.float32, f"{name}: cams").contiguous()
     if tuple(cams.shape) != (V, 12):
         raise HipError(f"{name}: cams [{V},12] (R row-major, t), got {tuple(cams.shape)}")
-    fx, fy, cx, cy = (c_float(float(v)) for v in intr)
-    return cams, (fx, fy, cx, cy)
+    return cams, tuple(intr)
 
 
 def render_clear(keys):
     """every key of keys int64 [V,H,W] to empty (bf_render_clear)"""
     V, H, W = _render_target("render_clear", keys)
-    _check(lib().bf_render_clear(_ptr(keys), c_int(V), c_int(H), c_int(W), _stream()), "bf_render_clear")
+    _check(lib().bf_render_clear(_ptr(keys), V, H, W, _stream()), "bf_render_clear")
 
 
 def _render_points_work(keys, xyz, rgb, cams, intr, near, far, radius, layer, stats=None):
@@ -1753,9 +1659,8 @@ def render_points(keys, xyz, rgb, cams, intr, near, far, radius, layer, stats=No
     if stats is not None and (_need(stats, torch.int64, "render_points: stats").numel() < 2):
         raise HipError("render_points: stats int64 [2]")
     cams, (fx, fy, cx, cy) = _render_cams("render_points", cams, V, intr)
-    _check(lib().bf_render_points(_ptr(xyz), _ptr(rgb), ctypes.c_longlong(n), _ptr(cams), c_int(V), fx, fy, cx, cy,
-                                  c_int(H), c_int(W), c_float(float(near)), c_float(float(far)), c_int(int(radius)),
-                                  c_int(int(layer)), _ptr(keys), _ptr(stats), _stream()), "bf_render_points")
+    _check(lib().bf_render_points(_ptr(xyz), _ptr(rgb), n, _ptr(cams), V, fx, fy, cx, cy, H, W, near, far,
+                                  int(radius), int(layer), _ptr(keys), _ptr(stats), _stream()), "bf_render_points")
 
 
 def _render_edges_work(keys, corners, colors, mask, cams, intr, near, half_width, layer):
@@ -1780,9 +1685,8 @@ def render_edges(keys, corners, colors, mask, cams, intr, near, half_width, laye
         if tuple(mask.shape) != (b,):
             raise HipError(f"render_edges: mask [{b}], got {tuple(mask.shape)}")
     cams, (fx, fy, cx, cy) = _render_cams("render_edges", cams, V, intr)
-    _check(lib().bf_render_edges(_ptr(corners), _ptr(colors), _ptr(mask), c_int(b), _ptr(cams), c_int(V), fx, fy, cx, cy,
-                                 c_int(H), c_int(W), c_float(float(near)), c_int(int(half_width)), c_int(int(layer)),
-                                 _ptr(keys), _stream()), "bf_render_edges")
+    _check(lib().bf_render_edges(_ptr(corners), _ptr(colors), _ptr(mask), b, _ptr(cams), V, fx, fy, cx, cy, H, W, near,
+                                 int(half_width), int(layer), _ptr(keys), _stream()), "bf_render_edges")
 
 
 RENDER_COOP_PIXELS = 64       # DESIGN.md §4 "Renderer": the sweep of scripts/render_mesh_probe.py
@@ -1814,10 +1718,9 @@ def render_triangles(keys, vertices, rgb, faces, cams, intr, near, far, cull, sh
         raise HipError("render_triangles: stats int64 [6]")
     cams, (fx, fy, cx, cy) = _render_cams("render_triangles", cams, V, intr)
     coop = RENDER_COOP_PIXELS if coop_pixels is None else min(int(coop_pixels), 2 ** 31 - 1)
-    _check(lib().bf_render_triangles(_ptr(vertices), _ptr(rgb), ctypes.c_longlong(n), _ptr(faces), ctypes.c_longlong(m),
-                                     _ptr(cams), c_int(V), fx, fy, cx, cy, c_int(H), c_int(W), c_float(float(near)),
-                                     c_float(float(far)), c_int(int(cull)), c_int(int(shade)), c_int(int(layer)),
-                                     c_int(coop), _ptr(keys), _ptr(stats), _stream()), "bf_render_triangles")
+    _check(lib().bf_render_triangles(_ptr(vertices), _ptr(rgb), n, _ptr(faces), m, _ptr(cams), V, fx, fy, cx, cy, H, W,
+                                     near, far, int(cull), int(shade), int(layer), coop, _ptr(keys), _ptr(stats),
+                                     _stream()), "bf_render_triangles")
 
 
 def _render_resolve_work(keys, background=(0, 0, 0)):
@@ -1840,8 +1743,8 @@ def render_resolve(keys, background=(0, 0, 0)):
             raise HipError("render_resolve: background (r, g, b)")
     rgb = torch.empty((V, H, W, 3), dtype=torch.uint8, device=keys.device)
     depth = torch.empty((V, H, W), dtype=torch.float32, device=keys.device)
-    _check(lib().bf_render_resolve(_ptr(keys), c_int(V), c_int(H), c_int(W), _ptr(image), c_int(const[0]), c_int(const[1]),
-                                   c_int(const[2]), _ptr(rgb), _ptr(depth), _stream()), "bf_render_resolve")
+    _check(lib().bf_render_resolve(_ptr(keys), V, H, W, _ptr(image), const[0], const[1], const[2], _ptr(rgb),
+                                   _ptr(depth), _stream()), "bf_render_resolve")
     return rgb, depth
 
 
@@ -1862,9 +1765,8 @@ def gt_frustum_seen(corners, pose_inv, fx, fy, cx, cy, W, H, near, far):
     pose_inv = _f64_rows(pose_inv, (4, 4), "gt_frustum_seen: pose_inv")
     n, m = corners.shape[0], pose_inv.shape[0]
     seen = torch.zeros((n, 8), dtype=torch.uint8, device=corners.device)
-    _check(lib().bf_gt_frustum(_ptr(corners), c_int(n), _ptr(pose_inv), c_int(m), c_double(fx), c_double(fy),
-                               c_double(cx), c_double(cy), c_int(int(W)), c_int(int(H)), c_double(near),
-                               c_double(far), _ptr(seen), _stream()), "bf_gt_frustum")
+    _check(lib().bf_gt_frustum(_ptr(corners), n, _ptr(pose_inv), m, fx, fy, cx, cy, int(W), int(H), near,
+                               far, _ptr(seen), _stream()), "bf_gt_frustum")
     return seen
 
 
@@ -1875,8 +1777,7 @@ def nn_min_dist2(query, points):
     points = _f64_rows(points, (3,), "nn_min_dist2: points")
     q, p = query.shape[0], points.shape[0]
     d2 = torch.full((q,), float("inf"), dtype=torch.float64, device=query.device)
-    _check(lib().bf_nn_min_dist2(_ptr(query), c_int(q), _ptr(points), ctypes.c_longlong(p), _ptr(d2), _stream()),
-           "bf_nn_min_dist2")
+    _check(lib().bf_nn_min_dist2(_ptr(query), q, _ptr(points), p, _ptr(d2), _stream()), "bf_nn_min_dist2")
     return d2
 
 
@@ -1888,7 +1789,7 @@ def obb_iou_exact(a, b, with_inter=False):
     p, g = a.shape[0], b.shape[0]
     iou = torch.empty((p, g), dtype=torch.float64, device=a.device)
     inter = torch.empty((p, g), dtype=torch.float64, device=a.device) if with_inter else None
-    _check(lib().bf_obb_iou_exact(_ptr(a), c_int(p), _ptr(b), c_int(g), _ptr(iou), _ptr(inter), _stream()),
+    _check(lib().bf_obb_iou_exact(_ptr(a), p, _ptr(b), g, _ptr(iou), _ptr(inter), _stream()),
            "bf_obb_iou_exact")
     return (iou, inter) if with_inter else iou
 
@@ -1929,12 +1830,11 @@ def gemm_fp8(a, w, scale, bias=None, act=None, resid=None, out=None, out_dtype=t
         _need(bias, torch.float32, "bias")
     if a.stride(1) != 1 or w.stride(1) != 1 or out.stride(1) != 1:
         raise HipError("gemm_fp8 operands need unit column stride")
-    _check(lib().bf_gemm_fp8_plan(c_void_p(a.data_ptr()), c_int(a.stride(0)), c_void_p(w.data_ptr()),
-                                  c_int(w.stride(0)), c_float(scale), _ptr(bias) if bias is not None else None,
-                                  c_void_p(resid.data_ptr()) if resid is not None else None,
-                                  c_int(resid.stride(0) if resid is not None else 0), c_void_p(out.data_ptr()),
-                                  c_int(out.stride(0)), c_int(_FP8_OUT[out.dtype]), c_float(out_qscale),
-                                  c_int(M), c_int(N), c_int(K), c_int(ACT[act]), _plan(plan), _stream()),
+    _check(lib().bf_gemm_fp8_plan(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), scale,
+                                  _ptr(bias) if bias is not None else None,
+                                  resid.data_ptr() if resid is not None else None,
+                                  resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0),
+                                  _FP8_OUT[out.dtype], out_qscale, M, N, K, ACT[act], _plan(plan), _stream()),
            "bf_gemm_fp8")
     return out
 
@@ -1948,9 +1848,9 @@ def layernorm_fp8(x, weight, bias, eps, qscale, out=None):
     _need(out, FP8, "out")
     if x.stride(1) != 1 or out.stride(1) != 1:
         raise HipError("layernorm_fp8: unit column stride")
-    _check(lib().bf_layernorm_fp8(c_void_p(x.data_ptr()), c_int(x.stride(0)), _ptr(weight), _ptr(bias),
-                                  c_float(eps), c_void_p(out.data_ptr()), c_int(out.stride(0)),
-                                  c_float(qscale), c_int(M), c_int(C), _stream()), "bf_layernorm_fp8")
+    _check(lib().bf_layernorm_fp8(x.data_ptr(), x.stride(0), _ptr(weight), _ptr(bias), eps,
+                                  out.data_ptr(), out.stride(0), qscale, M, C, _stream()),
+           "bf_layernorm_fp8")
     return out
 
 
@@ -1968,10 +1868,8 @@ def im2col_rgb8(img, pad, patch, mean, std, out=None, chw=False):
     n = B * (pad // patch) ** 2
     if out is None:
         out = torch.empty((n, 3 * patch * patch), dtype=torch.bfloat16, device=img.device)
-    _check(lib().bf_im2col_rgb8_chw(_ptr(img), c_int(B), c_int(H), c_int(W), c_int(int(chw)),
-                                    c_int(pad), c_int(patch), _f3(mean), _f3(std),
-                                    c_void_p(out.data_ptr()), c_int(out.stride(0)), _stream()),
-           "bf_im2col_rgb8_chw")
+    _check(lib().bf_im2col_rgb8_chw(_ptr(img), B, H, W, int(chw), pad, patch, _f3(mean), _f3(std),
+                                    out.data_ptr(), out.stride(0), _stream()), "bf_im2col_rgb8_chw")
     return out
 
 
@@ -1981,9 +1879,8 @@ def im2col_f32(x, pad, patch, out=None):
     n = B * (pad // patch) ** 2
     if out is None:
         out = torch.empty((n, patch * patch), dtype=torch.bfloat16, device=x.device)
-    _check(lib().bf_im2col_f32(_ptr(x), c_int(B), c_int(H), c_int(W), c_int(pad), c_int(patch),
-                               c_void_p(out.data_ptr()), c_int(out.stride(0)), _stream()),
-           "bf_im2col_f32")
+    _check(lib().bf_im2col_f32(_ptr(x), B, H, W, pad, patch, out.data_ptr(), out.stride(0),
+                               _stream()), "bf_im2col_f32")
     return out
 
 
@@ -1995,11 +1892,10 @@ def crop_resize_im2col(img, boxes, img_idx, size, patch, mean, std, kpad, out=No
     if out is None:
         out = torch.empty((N * (size // patch) ** 2, kpad), dtype=torch.bfloat16,
                           device=img.device)
-    _check(lib().bf_crop_resize_im2col(_ptr(img), c_int(H), c_int(W), _ptr(boxes),
-                                       _ptr(img_idx) if img_idx is not None else None, c_int(N),
-                                       c_int(size), c_int(patch), _f3(mean), _f3(std),
-                                       c_void_p(out.data_ptr()), c_int(out.stride(0)), _stream()),
-           "bf_crop_resize_im2col")
+    _check(lib().bf_crop_resize_im2col(_ptr(img), H, W, _ptr(boxes),
+                                       _ptr(img_idx) if img_idx is not None else None, N, size,
+                                       patch, _f3(mean), _f3(std), out.data_ptr(), out.stride(0),
+                                       _stream()), "bf_crop_resize_im2col")
     return out
 
 
@@ -2066,7 +1962,7 @@ def _timer():
 
 def new_depth_workspace(b, h, w, device):
     """a caller-owned zero-filled workspace for bf_depth_preprocess (one per concurrent user)"""
-    size = int(lib().bf_depth_standardize_workspace_size(c_int(b), c_int(h), c_int(w)))
+    size = int(lib().bf_depth_standardize_workspace_size(b, h, w))
     return torch.zeros(max(size, 1), dtype=torch.uint8, device=device)
 
 
@@ -2163,7 +2059,7 @@ def cu_placement(stream, n_wg=4096, spin=20000):
     """{(xcc, se, sh, cu)} of the CUs that n_wg probe workgroups ran on when launched on `stream`
     (bf_cu_probe): what a CU mask really does on this chip"""
     out = torch.zeros(2 * n_wg, dtype=torch.int32, device=torch.device("cuda", stream.device_index))
-    _check(lib().bf_cu_probe(_ptr(out), c_int(n_wg), c_int(spin), c_void_p(stream.cuda_stream)), "bf_cu_probe")
+    _check(lib().bf_cu_probe(_ptr(out), n_wg, spin, stream.cuda_stream), "bf_cu_probe")
     stream.synchronize()
     v = out.view(-1, 2).cpu().numpy()
     hw, xcc = v[:, 0], v[:, 1] & 0xF
@@ -2190,17 +2086,21 @@ def partition_cus(n_reserved, device=None, n_cu=None):
 # ------------------------------------------------------------------------------------------
 # CuTR decoder: cross-attention position bias + clip + softmax
 # ------------------------------------------------------------------------------------------
-def cpb_mlp(ref, pos, axis, w1, b1, w2):
-    """ref f32 [B,nq,4], pos f32 [n] -> f32 [B,nq,n,heads] (GlobalCrossAttention.rpe's MLP)"""
+def cpb_mlp(ref, pos, axis, w1, b1, w2, out=None):
+    """ref f32 [B,nq,4], pos f32 [n] -> f32 [B,nq,n,heads] (GlobalCrossAttention.rpe's MLP), written
+    into `out` when a preallocated buffer of that shape is given"""
     ref = _need(ref.contiguous(), torch.float32, "ref")
     B, nq = ref.shape[0], ref.shape[1]
     heads, hidden = w2.shape
-    out = torch.empty((B, nq, pos.shape[0], heads), dtype=torch.float32, device=ref.device)
-    _check(lib().bf_cpb_mlp(_ptr(ref), c_int(B), c_int(nq), _ptr(pos.contiguous()), c_int(pos.shape[0]),
-                            c_int(axis), _ptr(w1.contiguous()), _ptr(b1.contiguous()),
-                            _ptr(w2.contiguous()), c_int(hidden), c_int(heads), _ptr(out), _stream()),
-           "bf_cpb_mlp")
+    if out is None:
+        out = torch.empty((B, nq, pos.shape[0], heads), dtype=torch.float32, device=ref.device)
+    _check(lib().bf_cpb_mlp(_ptr(ref), B, nq, _ptr(pos.contiguous()), pos.shape[0], axis,
+                            _ptr(w1.contiguous()), _ptr(b1.contiguous()), _ptr(w2.contiguous()), hidden,
+                            heads, _ptr(out), _stream()), "bf_cpb_mlp")
     return out
+
+
+cpb_mlp_into = cpb_mlp      # the name decoder_engine calls it by, with `out` as the seventh argument
 
 
 def xattn(q, k, v, rx, ry, hh, ww, q0, heads, scale, out=None):
@@ -2218,12 +2118,10 @@ def xattn(q, k, v, rx, ry, hh, ww, q0, heads, scale, out=None):
     if q0 < Nq:
         rx = _need(rx.contiguous(), torch.float32, "rx")
         ry = _need(ry.contiguous(), torch.float32, "ry")
-    _check(lib().bf_xattn_f32(c_void_p(q.data_ptr()), c_int(q.stride(1)), c_void_p(k.data_ptr()),
-                              c_int(k.stride(1)), c_void_p(v.data_ptr()), c_int(v.stride(1)),
-                              _ptr(rx) if q0 < Nq else None, _ptr(ry) if q0 < Nq else None,
-                              c_void_p(out.data_ptr()), c_int(out.stride(1)), c_int(B), c_int(heads),
-                              c_int(Nq), c_int(q0), c_int(hh), c_int(ww), c_float(scale), _stream()),
-           "bf_xattn_f32")
+    _check(lib().bf_xattn_f32(q.data_ptr(), q.stride(1), k.data_ptr(), k.stride(1), v.data_ptr(),
+                              v.stride(1), _ptr(rx) if q0 < Nq else None,
+                              _ptr(ry) if q0 < Nq else None, out.data_ptr(), out.stride(1), B, heads,
+                              Nq, q0, hh, ww, scale, _stream()), "bf_xattn_f32")
     return out
 
 
@@ -2231,8 +2129,8 @@ def rpe_softmax(attn, rx, ry, hh, ww, q0):
     """attn f32 [B,H,Nq,hh*ww] in place: + bias on rows q >= q0, clip, softmax"""
     _need(attn, torch.float32, "attn")
     B, H, Nq, N = attn.shape
-    _check(lib().bf_rpe_softmax(_ptr(attn), c_int(B), c_int(H), c_int(Nq), c_int(q0), _ptr(rx),
-                                _ptr(ry), c_int(hh), c_int(ww), _stream()), "bf_rpe_softmax")
+    _check(lib().bf_rpe_softmax(_ptr(attn), B, H, Nq, q0, _ptr(rx), _ptr(ry), hh, ww, _stream()),
+           "bf_rpe_softmax")
     return attn
 
 
@@ -2270,9 +2168,8 @@ def gemm_f32(a, w, bias=None, act=None, resid=None, out=None, a_map=None, c_map=
                 raise HipError(f"gemm_f32: {n} shorter than M")
     if bias is not None:
         _need(bias, torch.float32, "bias")
-    _check(lib().bf_gemm_f32(pa, c_int(lda), _ptr(a_map), pw, c_int(ldw), _ptr(bias), pr, c_int(ldr),
-                             pc, c_int(ldc), _ptr(c_map), c_int(M), c_int(N), c_int(K), c_int(ACT[act]),
-                             _stream()), "bf_gemm_f32")
+    _check(lib().bf_gemm_f32(pa, lda, _ptr(a_map), pw, ldw, _ptr(bias), pr, ldr, pc, ldc, _ptr(c_map),
+                             M, N, K, ACT[act], _stream()), "bf_gemm_f32")
     return out
 
 
@@ -2285,9 +2182,8 @@ def ln_rows(x, gamma, beta, eps, out=None, pos=None, out2=None, gelu=False):
     po, ldo = _rows(out, "out")
     pp, ldp = _rows(pos, "pos")
     p2, ld2 = _rows(out2, "out2")
-    _check(lib().bf_ln_rows_f32(px, c_int(ldx), _ptr(gamma), _ptr(beta), c_float(eps), po, c_int(ldo),
-                                pp, c_int(ldp), p2, c_int(ld2), c_int(M), c_int(C), c_int(int(gelu)),
-                                _stream()), "bf_ln_rows_f32")
+    _check(lib().bf_ln_rows_f32(px, ldx, _ptr(gamma), _ptr(beta), eps, po, ldo, pp, ldp, p2, ld2, M,
+                                C, int(gelu), _stream()), "bf_ln_rows_f32")
     return out
 
 
@@ -2298,9 +2194,8 @@ def groupnorm_cl(x, frames, groups, gamma, beta, eps, out, pos=None, out2=None):
     pp, ldp = _rows(pos, "pos")
     p2, ld2 = _rows(out2, "out2")
     P = x.shape[0] // frames
-    _check(lib().bf_groupnorm_cl_f32(px, c_int(ldx), c_int(frames), c_int(P), c_int(x.shape[1]), c_int(groups),
-                                     _ptr(gamma), _ptr(beta), c_float(eps), po, c_int(ldo), pp, c_int(ldp),
-                                     p2, c_int(ld2), _stream()), "bf_groupnorm_cl_f32")
+    _check(lib().bf_groupnorm_cl_f32(px, ldx, frames, P, x.shape[1], groups, _ptr(gamma), _ptr(beta), eps, po,
+                                     ldo, pp, ldp, p2, ld2, _stream()), "bf_groupnorm_cl_f32")
     return out
 
 
@@ -2310,8 +2205,7 @@ def s2d(x, frames, H, W, out=None):
     if out is None:
         out = torch.empty((frames * (H // 2) * (W // 2), 4 * C), dtype=torch.float32, device=x.device)
     px, ldx = _rows(x, "x")
-    _check(lib().bf_s2d_f32(px, c_int(ldx), c_int(frames), c_int(H), c_int(W), c_int(C), _ptr(out), _stream()),
-           "bf_s2d_f32")
+    _check(lib().bf_s2d_f32(px, ldx, frames, H, W, C, _ptr(out), _stream()), "bf_s2d_f32")
     return out
 
 
@@ -2323,11 +2217,10 @@ def row_heads(x, in_fs, in_off, rows, nq, w, b, mode, out=None, prop=None, param
     """the predictors' output linears + transforms (bf_row_heads_f32; see bf_dec_native.hip)"""
     px, ldx = _rows(x, "x")
     po, ldo = _rows(out, "out")
-    _check(lib().bf_row_heads_f32(px, c_int(ldx), c_int(in_fs), c_int(in_off), c_int(rows), c_int(nq),
-                                  c_int(w.shape[1]), _ptr(w), _ptr(b), c_int(w.shape[0]), _ptr(prop),
-                                  _ptr(params), po, c_int(ldo), _ptr(boxes), c_float(clamp_wh[0]),
-                                  c_float(clamp_wh[1]), c_float(max_ratio), c_int(HEAD_MODES[mode]),
-                                  _stream()), "bf_row_heads_f32")
+    _check(lib().bf_row_heads_f32(px, ldx, in_fs, in_off, rows, nq, w.shape[1], _ptr(w), _ptr(b),
+                                  w.shape[0], _ptr(prop), _ptr(params), po, ldo, _ptr(boxes),
+                                  clamp_wh[0], clamp_wh[1], max_ratio, HEAD_MODES[mode], _stream()),
+           "bf_row_heads_f32")
     return out
 
 
@@ -2335,8 +2228,8 @@ def topk_rows(v, frames, n, k, ldv=1, idx=None, vals=None):
     """per-frame top-k of v[(f*n + i)*ldv] (descending, ties -> lower index): int32 idx [frames, k]"""
     if idx is None:
         idx = torch.empty((frames, k), dtype=torch.int32, device=v.device)
-    _check(lib().bf_topk_rows_f32(c_void_p(v.data_ptr()), c_int(ldv), c_int(frames), c_int(n), c_int(k),
-                                  _ptr(idx), _ptr(vals), _stream()), "bf_topk_rows_f32")
+    _check(lib().bf_topk_rows_f32(v.data_ptr(), ldv, frames, n, k, _ptr(idx), _ptr(vals), _stream()),
+           "bf_topk_rows_f32")
     return idx
 
 
@@ -2344,10 +2237,9 @@ def prop_select(boxes, frames, n, k, idx, ref, embs, max_e, qpos, qfs, qoff):
     """ref[f*k + j] = boxes[f*n + idx[f, j]]; qpos row f*qfs + qoff + j = the 4 box embeddings"""
     pq, ldq = _rows(qpos, "qpos")
     ex, ey, ew, eh = embs
-    _check(lib().bf_prop_select_f32(_ptr(boxes), c_int(frames), c_int(n), c_int(k), _ptr(idx), _ptr(ref),
-                                    _ptr(ex), _ptr(ey), _ptr(ew), _ptr(eh), c_int(ex.shape[1]),
-                                    c_float(max_e), pq, c_int(ldq), c_int(qfs), c_int(qoff), _stream()),
-           "bf_prop_select_f32")
+    _check(lib().bf_prop_select_f32(_ptr(boxes), frames, n, k, _ptr(idx), _ptr(ref), _ptr(ex), _ptr(ey),
+                                    _ptr(ew), _ptr(eh), ex.shape[1], max_e, pq, ldq, qfs, qoff,
+                                    _stream()), "bf_prop_select_f32")
 
 
 def infer_select(logits, frames, nq, nc, boxes, b3info, desc, desc_fs, desc_off, Kinv, Tg, img_wh, k, outs):
@@ -2355,10 +2247,9 @@ def infer_select(logits, frames, nq, nc, boxes, b3info, desc, desc_fs, desc_off,
     scores [F,k], classes int64 [F,k], logits [F,k,nc], boxes [F,k,4], proj [F,k,2], b3 [F,k,6],
     R [F,k,3,3], desc [F,k,C]"""
     pd, ldd = _rows(desc, "desc")
-    _check(lib().bf_infer_select_f32(_ptr(logits), c_int(frames), c_int(nq), c_int(nc), _ptr(boxes),
-                                     _ptr(b3info), pd, c_int(ldd), c_int(desc_fs), c_int(desc_off),
-                                     c_int(desc.shape[1]), _ptr(Kinv), _ptr(Tg), _ptr(img_wh), c_int(k),
-                                     _ptr(outs["scores"]), _ptr(outs["classes"]), _ptr(outs["logits"]),
+    _check(lib().bf_infer_select_f32(_ptr(logits), frames, nq, nc, _ptr(boxes), _ptr(b3info), pd, ldd,
+                                     desc_fs, desc_off, desc.shape[1], _ptr(Kinv), _ptr(Tg), _ptr(img_wh),
+                                     k, _ptr(outs["scores"]), _ptr(outs["classes"]), _ptr(outs["logits"]),
                                      _ptr(outs["boxes"]), _ptr(outs["proj"]), _ptr(outs["b3"]),
                                      _ptr(outs["R"]), _ptr(outs["desc"]), _stream()), "bf_infer_select_f32")
 
@@ -2367,9 +2258,8 @@ def ray_fourier(K3, W, H, feat, stride, scales, out):
     """CameraRayEmbedding's Fourier features of one camera into out [feat*feat, ld] (ld >= 3 * bands)"""
     K3 = np.asarray(K3, np.float32).reshape(3, 3)
     po, ld = _rows(out, "out")
-    _check(lib().bf_ray_fourier_f32(c_float(K3[0, 0]), c_float(K3[1, 1]), c_float(K3[0, 2]), c_float(K3[1, 2]),
-                                    c_int(W), c_int(H), c_int(feat), c_int(stride), _ptr(scales),
-                                    c_int(scales.shape[0]), po, c_int(ld), _stream()), "bf_ray_fourier_f32")
+    _check(lib().bf_ray_fourier_f32(K3[0, 0], K3[1, 1], K3[0, 2], K3[1, 2], W, H, feat, stride, _ptr(scales),
+                                    scales.shape[0], po, ld, _stream()), "bf_ray_fourier_f32")
     return out
 
 
@@ -2380,15 +2270,6 @@ def self_attn(q, k, v, out, frames, heads, n, q0, scale):
     pk, ldk = _rows(k, "k")
     pv, ldv = _rows(v, "v")
     po, ldo = _rows(out, "out")
-    _check(lib().bf_self_attn_f32(pq, c_int(ldq), pk, c_int(ldk), pv, c_int(ldv), po, c_int(ldo), c_int(frames),
-                                  c_int(heads), c_int(n), c_int(q0), c_float(scale), _stream()), "bf_self_attn_f32")
-    return out
-
-
-def cpb_mlp_into(ref, pos, axis, w1, b1, w2, out):
-    """cpb_mlp into a preallocated [B, nq, n, heads] buffer"""
-    B, nq = ref.shape[0], ref.shape[1]
-    heads, hidden = w2.shape
-    _check(lib().bf_cpb_mlp(_ptr(ref), c_int(B), c_int(nq), _ptr(pos), c_int(pos.shape[0]), c_int(axis), _ptr(w1),
-                            _ptr(b1), _ptr(w2), c_int(hidden), c_int(heads), _ptr(out), _stream()), "bf_cpb_mlp")
+    _check(lib().bf_self_attn_f32(pq, ldq, pk, ldk, pv, ldv, po, ldo, frames, heads, n, q0, scale, _stream()),
+           "bf_self_attn_f32")
     return out

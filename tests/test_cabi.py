@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from boxfusion_amd import build as B
 
 HEADER = os.path.join(os.path.dirname(B.HERE), "include", "boxfusion_hip.h")
@@ -11,7 +13,7 @@ HEADER = os.path.join(os.path.dirname(B.HERE), "include", "boxfusion_hip.h")
 
 def declared():
     src = open(HEADER).read()
-    return sorted(set(re.findall(r"^\s*(?:const\s+char\*|int|size_t)\s+(bf_\w+)\s*\(", src, re.M)))
+    return sorted(set(re.findall(r"^\s*(?:const\s+char\*|int|size_t|void)\s+(bf_\w+)\s*\(", src, re.M)))
 
 
 def test_header_declares_entry_points():
@@ -47,3 +49,112 @@ def test_gemm_abi_is_stateless():
     fields = re.findall(r"int32_t\s+(\w+);", body)
     assert [f for f, _ in _lib.GemmPlan._fields_] == fields
     assert ctypes.sizeof(_lib.GemmPlan) == 4 * len(fields)
+
+
+# ---- the binding takes its types from the header (boxfusion_amd/_abi.py) --------------------------
+def param_counts():
+    """{entry point: parameter count} by commas, with this file's own regular expressions"""
+    src = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\b(bf_\w+)\s*\(([^()]*)\)\s*;", src):
+        out[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    return out
+
+
+def test_reader_finds_every_prototype_and_lib_types_it():
+    from boxfusion_amd import _abi, _lib
+    names = declared()
+    assert len(names) == 110
+    assert sorted(_abi.prototypes()) == names
+    B.build()
+    lib, counts = _lib.lib(), param_counts()
+    assert sorted(counts) == names
+    for n in names:
+        f = getattr(lib, n)
+        assert f.argtypes is not None and len(f.argtypes) == counts[n], n
+
+
+def test_signatures_spot_checks():
+    from boxfusion_amd import _lib
+    B.build()
+    lib = _lib.lib()
+    c = ctypes
+    assert (lib.bf_version.restype, list(lib.bf_version.argtypes)) == (c.c_char_p, [])
+    f = lib.bf_obb_iou_workspace_size
+    assert (f.restype, list(f.argtypes)) == (c.c_size_t, [c.c_int])
+    f = lib.bf_cloud_blocks
+    assert (f.restype, list(f.argtypes)) == (c.c_size_t, [c.c_longlong, c.c_int])
+    assert lib.bf_fseq_destroy.restype is None and list(lib.bf_fseq_destroy.argtypes) == [c.c_void_p]
+    a = list(lib.bf_icp_reduce.argtypes)
+    assert len(a) == 20 and a[11:17] == [c.c_double] * 6 and a[-1] is c.c_void_p
+    assert lib.bf_icp_reduce.restype is c.c_int
+    assert a[:11] == [c.c_void_p, c.c_void_p, c.c_int, c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_void_p,
+                      c.c_int, c.c_int, c.c_void_p]
+
+
+def test_host_entry_points_through_the_typed_handle():
+    from boxfusion_amd import _lib
+    B.build()
+    lib = _lib.lib()
+    assert lib.bf_icp_blocks(480, 640, 4) == 19
+    assert lib.bf_cloud_blocks(1000, 3) == 12
+    assert lib.bf_cloud_blocks(1 << 40, 1) == 1 << 32          # a size_t, not truncated to an int
+    assert _lib.icp_blocks(480, 640, 4) == 19
+    with pytest.raises(TypeError):
+        lib.bf_icp_blocks(480, 640)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.bf_icp_blocks(480, 640, 4.0)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.bf_cloud_blocks(1000.0, 3)
+
+
+I, I32, I64, F, D, P = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double,
+                        ctypes.c_void_p)
+# written out from the hand-made mirrors the binding had before it read the header
+STRUCTS = {
+    "RowsField": [("a", P), ("b", P), ("dst", P), ("n_a", I64), ("n_b", I64), ("row_bytes", I32), ("pad", I32)],
+    "FilterCfg": [("score_thresh", F), ("floor_ratio", F), ("floor_half", F), ("size_max", F), ("gap_w", I32),
+                  ("gap_h", I32), ("W", I32), ("H", I32), ("use_score", I32), ("use_uv", I32), ("use_floor", I32),
+                  ("use_large", I32)],
+    "NmsCfg": [("iou_threshold", D), ("translation_gap", F), ("rotation_gap", F), ("center_gap", D),
+               ("max_list", I), ("list_capacity", I)],
+    "CorrCfg": [("small_size", D), ("threshold", D), ("translation_gap", F), ("rotation_gap", F), ("W", F), ("H", F),
+                ("max_list", I), ("list_capacity", I)],
+    "FuseCfg": [("iters", I), ("pst_size", I), ("max_accept", I), ("legacy_promotion", I), ("center_init", D),
+                ("shape_init", D), ("center_coef", D), ("shape_coef", D), ("beta", D), ("min_scale", D),
+                ("img_h", F), ("img_w", F), ("K", F * 16)],
+    "FseqCfg": [("nms", "NmsCfg"), ("corr", "CorrCfg"), ("fuse", "FuseCfg"), ("use_fusion", I32),
+                ("strict_hull", I32)],
+    "GemmPlan": [("cu_budget", I32), ("tile_rows", I32), ("kernel", I32), ("variant", I32), ("group_m", I32),
+                 ("balanced", I32), ("objective", I32)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(STRUCTS))
+def test_struct_mirror_has_the_hand_written_layout(name):
+    from boxfusion_amd import _lib
+    cls = getattr(_lib, name)
+    assert issubclass(cls, ctypes.Structure)
+    want = [(f, getattr(_lib, t) if isinstance(t, str) else t) for f, t in STRUCTS[name]]
+    assert list(cls._fields_) == want
+
+
+def test_struct_sizes_and_offsets():
+    from boxfusion_amd import _lib
+    assert ctypes.sizeof(_lib.NmsCfg) == 32 and ctypes.sizeof(_lib.CorrCfg) == 40
+    assert ctypes.sizeof(_lib.FuseCfg) == 136
+    assert _lib.FuseCfg.K.offset == 72
+    assert ctypes.sizeof(_lib.FseqCfg) == 32 + 40 + 136 + 8 == 216
+    assert ctypes.sizeof(_lib.RowsField) == 48 and ctypes.sizeof(_lib.FilterCfg) == 48
+
+
+def test_reader_refuses_a_type_it_does_not_know():
+    from boxfusion_amd import _abi
+    assert _abi._ctype("const  float *", "bf_f, parameter 1", _abi._SCALAR) is ctypes.c_void_p
+    with pytest.raises(TypeError, match=r"bf_s\.b.*'unsigned'"):
+        _abi._ctype("unsigned", "bf_s.b", _abi._SCALAR)
+
+
+def test_lib_py_assigns_no_signatures_of_its_own():
+    from boxfusion_amd import _lib
+    assert not re.search(r"\.(restype|argtypes)\b", open(_lib.__file__).read())
