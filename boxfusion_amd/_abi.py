@@ -1,8 +1,9 @@
 """The C types of libboxfusion_hip.so, read from include/boxfusion_hip.h: the one place they are written.
 
 The header is regular: an entry point is `ret bf_name(type name, ...);`, a struct is
-`typedef struct { fields } bf_name;`.  A few regular expressions read those two forms (this is no C
-parser); a type that the tables below do not hold raises and names the function or field.
+`typedef struct { fields } bf_name;`, a constant is `#define BF_NAME value` or an enum member.  A few
+regular expressions read those forms (this is no C parser); a type that the tables below do not hold,
+or a constant's value that is no integer literal, raises and names the function, field or constant.
 """
 import ctypes
 import functools
@@ -65,6 +66,58 @@ def prototypes():
         out[name] = (_RETURN[ret], [_ctype(re.sub(r"\w+\s*$", "", p), f"{name}, parameter {i + 1}", _SCALAR)
                                     for i, p in enumerate(params)])
     return out
+
+
+# an integer literal (decimal or hex, u / l / ll suffixes), optionally `<<` a second one, optionally in parentheses
+_LITERAL = r"(-?\s*(?:0[xX][0-9a-fA-F]+|\d+))[uUlL]{0,3}"
+_VALUE = re.compile(r"%s(?:\s*<<\s*%s)?" % (_LITERAL, _LITERAL))
+
+
+def _value(text, name):
+    inner = text.strip()
+    if inner.startswith("(") and inner.endswith(")"):
+        inner = inner[1:-1].strip()
+    m = _VALUE.fullmatch(inner)
+    if m is None:
+        raise ValueError(f"{HEADER}: {name}: cannot read the value {text.strip()!r}")
+    v = int(m.group(1).replace(" ", ""), 0)
+    return v << int(m.group(2), 0) if m.group(2) else v
+
+
+def _enums(src):
+    """[{member: int}] per enum body, in the header's order; a member without a value is the one before it plus one"""
+    out = []
+    for body in re.findall(r"\benum\b[^{;]*\{([^{}]*)\}", src):
+        members, nxt = {}, 0
+        for member in filter(None, (m.strip() for m in body.split(","))):
+            name, _, text = member.partition("=")
+            name = name.strip()
+            members[name] = nxt = _value(text, name) if text else nxt
+            nxt += 1
+        out.append(members)
+    return out
+
+
+def constants(source=None):
+    """{name: int} of every object-like `#define BF_NAME value` and every enum member; `source`: header
+    text to read instead of the header"""
+    src = _source() if source is None else source
+    out = {}
+    for name, call, text in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(BF_\w+)(\()?(.*)$", src, re.M):
+        if not call:                                   # a function-like macro is no constant
+            out[name] = _value(text, name)
+    for members in _enums(src):
+        out.update(members)
+    return out
+
+
+def enum_names(prefix, source=None):
+    """the members of the one enum whose members all start with `prefix`, in value order, the prefix stripped
+    and lower-cased: the names of a counter tensor's words from the enum of its indices"""
+    found = [e for e in _enums(_source() if source is None else source) if e and all(k.startswith(prefix) for k in e)]
+    if len(found) != 1:
+        raise KeyError(f"{HEADER}: {len(found)} enums whose members all start with {prefix}")
+    return tuple(k[len(prefix):].lower() for k in sorted(found[0], key=found[0].get))
 
 
 def declare(lib):

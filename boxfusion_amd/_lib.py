@@ -26,17 +26,19 @@ _LIB = None
 
 c_float, c_void_p = ctypes.c_float, ctypes.c_void_p
 
-BF_DEV_FUSION_LIST_OVERFLOW = 1
-BF_DEV_HULL_OVERFLOW = 2
-BF_DEV_VIEW_OVERFLOW = 4
-BF_DEV_INDEX_RANGE = 8
-BF_DEV_HULL_TRUNC = 16
+_C = _abi.constants()           # the header's #defines and enum members: every layout number below is read here
+BF_DEV_FUSION_LIST_OVERFLOW, BF_DEV_HULL_OVERFLOW, BF_DEV_VIEW_OVERFLOW, BF_DEV_INDEX_RANGE, BF_DEV_HULL_TRUNC = (
+    _C["BF_DEV_" + n] for n in ("FUSION_LIST_OVERFLOW", "HULL_OVERFLOW", "VIEW_OVERFLOW", "INDEX_RANGE", "HULL_TRUNC"))
+STATS_WORDS, ICP_ROW, ROWS_MAX_FIELDS, FSEQ_STATE_N = (      # STATS_WORDS: of every int64 stats / counters tensor
+    _C["BF_" + n] for n in ("STATS_WORDS", "ICP_ROW", "ROWS_MAX_FIELDS", "FSEQ_STATE_N"))
 
 # the header's structs (all-zero GemmPlan = the product defaults)
 NmsCfg, CorrCfg, FuseCfg, FseqCfg, FilterCfg, RowsField, GemmPlan = map(_abi.struct, (
     "bf_nms_cfg", "bf_corr_cfg", "bf_fuse_cfg", "bf_fseq_cfg", "bf_filter_cfg", "bf_rows_field", "bf_gemm_plan"))
 
-ROWS_MAX_FIELDS = 16
+
+def _bits(prefix, **messages):                      # {status bit of the header: message}
+    return {_C[prefix + k]: v for k, v in messages.items()}
 
 
 class HipError(RuntimeError):
@@ -382,9 +384,6 @@ def fusion_fitness(box, R, view_pose, view_tc, pst, search_size, cfg: FuseCfg):
 # ------------------------------------------------------------------------------------------
 # keyframe sequencer (bf_fseq_*)
 # ------------------------------------------------------------------------------------------
-FSEQ_STATE_N = 16
-
-
 class FusionSequencer:
     """Owner of one bf_fseq: the demo.py:200-305 keyframe sequence over batches of keyframes,
     all_pred_box on the device and BoxManager's lists in the library (include/boxfusion_hip.h).
@@ -845,8 +844,9 @@ def ingest_rgbd(bgr, depth_u16, depth_scale, rot_k=0, rgb_out=None, depth_out=No
     return rgb_out, depth_out
 
 
-PNG_STATUS = {1: "bad signature", 2: "bad IHDR", 4: "unsupported PNG kind", 8: "bad chunk list",
-              16: "bad zlib / deflate stream", 32: "Adler-32 mismatch", 64: "bad row filter", 128: "size mismatch"}
+PNG_STATUS = _bits("BF_PNG_", BAD_SIGNATURE="bad signature", BAD_HEADER="bad IHDR", UNSUPPORTED="unsupported PNG kind",
+                   BAD_CHUNK="bad chunk list", BAD_ZLIB="bad zlib / deflate stream", BAD_ADLER="Adler-32 mismatch",
+                   BAD_FILTER="bad row filter", SIZE="size mismatch")
 
 
 def _decode_batch(name, entry, workspace_bytes, status_bits, noun, data, offsets, H, W, tail, dtype, out,
@@ -914,8 +914,8 @@ def png_workspace_bytes(F, H, W, total_file_bytes):
     return int(lib().bf_png_workspace_bytes(F, H, W, total_file_bytes))
 
 
-ZLIB_STATUS = {8: "shorter than a zlib header + Adler-32", 16: "bad zlib / deflate stream", 32: "Adler-32 mismatch",
-               128: "inflated length is not 2 H W"}
+ZLIB_STATUS = _bits("BF_PNG_", BAD_CHUNK="shorter than a zlib header + Adler-32", BAD_ZLIB="bad zlib / deflate stream",
+                    BAD_ADLER="Adler-32 mismatch", SIZE="inflated length is not 2 H W")
 
 
 def zlib_decode_u16(streams, offsets, H, W, out=None, offsets_host=None, check=True, depth_scale=None, work=None):
@@ -950,8 +950,9 @@ def png_rgb_workspace_bytes(F, H, W, total_file_bytes):
     return int(lib().bf_png_rgb_workspace_bytes(F, H, W, total_file_bytes))
 
 
-JPEG_STATUS = {1: "bad / missing marker segment", 2: "unsupported JPEG kind (not baseline 1/3-component h2v2/h2v1/h1v1)",
-               4: "size mismatch", 8: "corrupt entropy-coded data"}
+JPEG_STATUS = _bits("BF_JPG_", BAD_MARKER="bad / missing marker segment",
+                    UNSUPPORTED="unsupported JPEG kind (not baseline 1/3-component h2v2/h2v1/h1v1)", SIZE="size mismatch",
+                    BAD_DATA="corrupt entropy-coded data")
 
 
 def jpeg_decode_rgb(files, offsets, H, W, out=None, check=True, work=None, offsets_host=None):
@@ -1118,8 +1119,8 @@ def cloud_pack(xyz, valid, rgb):
     return out, offsets
 
 
-CLOUD_SLOT_WORDS = 5            # int64 words of a voxel slot: key, then eight uint32 (bf_cloud_integrate)
-CLOUD_STATS = ("stored", "nonfinite", "out_of_range", "dropped_full", "saturated", "runs")
+# CLOUD_SLOT_WORDS: int64 words of a voxel slot: key, then eight uint32 (bf_cloud_integrate)
+CLOUD_SLOT_WORDS, CLOUD_STATS = _C["BF_CLOUD_SLOT_WORDS"], _abi.enum_names("BF_CLOUD_STAT_")
 
 
 def cloud_table(capacity, device):
@@ -1129,7 +1130,7 @@ def cloud_table(capacity, device):
         raise HipError("cloud_table: capacity must be a power of two below 2^31")
     table = torch.zeros((capacity, CLOUD_SLOT_WORDS), dtype=torch.int64, device=device)
     table[:, 0] = -1
-    return table, torch.zeros(8, dtype=torch.int64, device=device)
+    return table, torch.zeros(STATS_WORDS, dtype=torch.int64, device=device)
 
 
 def _cloud_integrate_work(xyz, valid, rgb, fine_step, table, stats, merge=True):
@@ -1151,7 +1152,7 @@ def cloud_integrate(xyz, valid, rgb, fine_step, table, stats, merge=True):
         raise HipError("cloud_integrate: xyz [...,3], valid [...], rgb [...,3] of the same points")
     _need(table, torch.int64, "cloud_integrate: table")
     _need(stats, torch.int64, "cloud_integrate: stats")
-    if table.dim() != 2 or table.shape[1] != CLOUD_SLOT_WORDS or stats.numel() < 8:
+    if table.dim() != 2 or table.shape[1] != CLOUD_SLOT_WORDS or stats.numel() < STATS_WORDS:
         raise HipError("cloud_integrate: table [capacity,5] / stats [8] of cloud_table")
     _check(lib().bf_cloud_integrate(_ptr(xyz), _ptr(valid), _ptr(rgb), n, fine_step, _ptr(table), table.shape[0],
                                     _ptr(stats), int(bool(merge)), _stream()), "bf_cloud_integrate")
@@ -1181,9 +1182,10 @@ def cloud_extract(table):
 # ------------------------------------------------------------------------------------------
 # scene mesh (bf_tsdf.hip)
 # ------------------------------------------------------------------------------------------
-TSDF_VOX, TSDF_FIELDS = 512, 6          # voxels of a block; int32 fields per voxel: w, sum q, cw, sum r g b
-TSDF_MAX_WEIGHT = 1 << 20
-TSDF_STATS = ("observations", "skipped_pose", "out_of_range", "dropped_full", "saturated", "blocks")
+# voxels of a block; int32 fields per voxel: w, sum q, cw, sum r g b; frames of one touch / update launch
+TSDF_VOX, TSDF_FIELDS, TSDF_MAX_WEIGHT, TSDF_MAX_FRAMES = (
+    _C["BF_TSDF_" + n] for n in ("VOX", "FIELDS", "MAX_WEIGHT", "MAX_FRAMES"))
+TSDF_STATS, TSDF_RAYCAST_STATS = _abi.enum_names("BF_TSDF_STAT_"), _abi.enum_names("BF_TSDF_RAY_")
 
 
 def tsdf_volume(capacity, device):
@@ -1195,14 +1197,14 @@ def tsdf_volume(capacity, device):
     return (torch.full((capacity,), -1, dtype=torch.int64, device=device),
             torch.zeros(capacity, dtype=torch.int64, device=device),
             torch.zeros((capacity, TSDF_FIELDS, TSDF_VOX), dtype=torch.int32, device=device),
-            torch.zeros(8, dtype=torch.int64, device=device))
+            torch.zeros(STATS_WORDS, dtype=torch.int64, device=device))
 
 
 def _tsdf_frames(name, depth, poses, rgb=None):
     depth = _need(depth, torch.float32, f"{name}: depth").contiguous()
     poses = _need(poses, torch.float32, f"{name}: poses").contiguous()
-    if depth.dim() != 3 or not 0 < depth.shape[0] <= 64 or tuple(poses.shape) != (depth.shape[0], 4, 4):
-        raise HipError(f"{name}: depth [B,H,W] and poses [B,4,4] of 1..64 frames; got {tuple(depth.shape)}, "
+    if depth.dim() != 3 or not 0 < depth.shape[0] <= TSDF_MAX_FRAMES or tuple(poses.shape) != (depth.shape[0], 4, 4):
+        raise HipError(f"{name}: depth [B,H,W] and poses [B,4,4] of 1..{TSDF_MAX_FRAMES} frames; got {tuple(depth.shape)}, "
                        f"{tuple(poses.shape)}")
     if rgb is not None:
         rgb = _need(rgb, torch.uint8, f"{name}: rgb").contiguous()
@@ -1219,8 +1221,8 @@ def _tsdf_arrays(name, keys, touched, vox=None, stats=None):
         raise HipError(f"{name}: keys / touched [capacity] of tsdf_volume")
     if vox is not None and (vox.dtype != torch.int32 or tuple(vox.shape) != (cap, TSDF_FIELDS, TSDF_VOX)):
         raise HipError(f"{name}: vox int32 [capacity,6,512] of tsdf_volume")
-    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 8):
-        raise HipError(f"{name}: stats int64 [8] of tsdf_volume")
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < STATS_WORDS):
+        raise HipError(f"{name}: stats int64 [{STATS_WORDS}] of tsdf_volume")
     return cap
 
 
@@ -1323,9 +1325,6 @@ def tsdf_surface(keys, vox, skey, sslot, voxel):
     return verts, vrgb, faces[:2 * nq]
 
 
-TSDF_RAYCAST_STATS = ("hits", "behind", "left_range", "skipped_pose", "no_normal")
-
-
 def _tsdf_raycast_work(keys, vox, poses, intr, H, W, voxel, trunc_voxels, near, far, min_weight, max_steps, counters,
                        colour=False):
     n = float(poses.shape[0]) * H * W
@@ -1345,8 +1344,8 @@ def tsdf_raycast(keys, vox, poses, intr, H, W, voxel, trunc_voxels, near, far, m
         raise HipError("tsdf_raycast: keys [capacity] and vox int32 [capacity,6,512] of tsdf_volume")
     if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4) or poses.shape[0] < 1:
         raise HipError(f"tsdf_raycast: poses [V,4,4], got {tuple(poses.shape)}")
-    if counters.dtype != torch.int64 or counters.numel() < 8:
-        raise HipError("tsdf_raycast: counters int64 [8]")
+    if counters.dtype != torch.int64 or counters.numel() < STATS_WORDS:
+        raise HipError(f"tsdf_raycast: counters int64 [{STATS_WORDS}]")
     V, H, W = int(poses.shape[0]), int(H), int(W)
     depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
     vertex = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
@@ -1401,11 +1400,11 @@ def _reduce_setup(name, live_vertex, stride, T, w2c, w2c_name, intr, out):
         raise HipError(f"{name}: T and {w2c_name} f64 [3,4]")
     H, W = live_vertex.shape[:2]
     dev = live_vertex.device
-    partials = torch.empty((icp_blocks(H, W, stride), 32), dtype=torch.float64, device=dev)
+    partials = torch.empty((icp_blocks(H, W, stride), ICP_ROW), dtype=torch.float64, device=dev)
     if out is None:
-        out = torch.empty(32, dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or out.numel() != 32:
-        raise HipError(f"{name}: out f64 [32]")
+        out = torch.empty(ICP_ROW, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != ICP_ROW:
+        raise HipError(f"{name}: out f64 [{ICP_ROW}]")
     return stride, T, M, [float(np.float32(v)) for v in intr], partials, out
 
 
@@ -1499,8 +1498,7 @@ def photo_reduce(live_vertex, live_intensity, stride, T, ref_intensity, ref_dept
 # ------------------------------------------------------------------------------------------
 # relocalisation (bf_fern.hip)
 # ------------------------------------------------------------------------------------------
-FERN_COUNTERS = ("observed", "added", "dropped_full")
-FERN_K_MAX = 8
+FERN_COUNTERS, FERN_K_MAX = _abi.enum_names("BF_FERN_COUNT_"), _C["BF_FERN_K_MAX"]
 
 
 def fern_upload(table, cells, device):

@@ -13,9 +13,6 @@
 // A field holds at most 255 * 2^24 < 2^32, so the packed 64-bit adds never carry from the low field into the high.
 #include "bf_compact.h"
 
-#define CLOUD_SLOT_WORDS 5
-#define CLOUD_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define CLOUD_MAX_COUNT (1u << 24)
 #define PIL_PRECISION_BITS 22
 
 // ---- Pillow 8-bit resample passes ------------------------------------------------------------------------------
@@ -104,37 +101,31 @@ BF_API int bf_resize_bicubic_u8(const uint8_t* src, int F, int Hs, int Ws, int H
     return bf_check_launch();
 }
 
-// ---- stable compaction: block counts, their scan, the scatter ---------------------------------------------------
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_pack_count(const uint8_t* __restrict__ valid, int hw, int bpf,
-                                                            int* __restrict__ counts) {
-    const int f = blockIdx.x / bpf, j = blockIdx.x - f * bpf;
-    const int p = j * CLOUD_BLOCK + threadIdx.x;
-    const bool sel = p < hw && valid[(size_t)f * hw + p] != 0;
-    int tot;
-    block_rank(sel, tot);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_pack_scatter(const float* __restrict__ xyz, const uint8_t* __restrict__ valid,
-                                                              const uint8_t* __restrict__ rgb, int hw, int bpf,
-                                                              const int* __restrict__ prefix, float* __restrict__ out) {
-    const int f = blockIdx.x / bpf, j = blockIdx.x - f * bpf;
-    const int p = j * CLOUD_BLOCK + threadIdx.x;
-    const size_t px = (size_t)f * hw + p;
-    const bool sel = p < hw && valid[px] != 0;
-    int tot;
-    const int r = block_rank(sel, tot);
-    if (!sel) return;
-    float* o = out + ((size_t)prefix[blockIdx.x] + r) * 6;
-    const float* s = xyz + px * 3;
-    const uint8_t* c = rgb + px * 3;
-    o[0] = s[0];
-    o[1] = s[1];
-    o[2] = s[2];
-    o[3] = (float)c[0] / 255.0f;
-    o[4] = (float)c[1] / 255.0f;
-    o[5] = (float)c[2] / 255.0f;
-}
+// ---- bf_cloud_pack: the valid pixels of B frames, compacted (bf_compact.h) ----------------------------------------------
+struct PackSel {                                                 // block b = frame b / bpf's block b % bpf
+    const float* xyz;
+    const uint8_t* valid;
+    const uint8_t* rgb;
+    int hw, bpf;
+    float* out;
+    __device__ bool selected(unsigned b, unsigned t) const {
+        const int f = b / bpf, j = b - f * bpf, p = j * CLOUD_BLOCK + t;
+        return p < hw && valid[(size_t)f * hw + p] != 0;
+    }
+    __device__ void write(unsigned b, unsigned t, size_t row) const {
+        const int f = b / bpf, j = b - f * bpf, p = j * CLOUD_BLOCK + t;
+        const size_t px = (size_t)f * hw + p;
+        float* o = out + row * 6;
+        const float* s = xyz + px * 3;
+        const uint8_t* c = rgb + px * 3;
+        o[0] = s[0];
+        o[1] = s[1];
+        o[2] = s[2];
+        o[3] = (float)c[0] / 255.0f;
+        o[4] = (float)c[1] / 255.0f;
+        o[5] = (float)c[2] / 255.0f;
+    }
+};
 
 BF_API size_t bf_cloud_blocks(long long items_per_group, int groups) {
     if (items_per_group <= 0 || groups <= 0) return 0;
@@ -148,41 +139,12 @@ BF_API int bf_cloud_pack(const float* xyz, const uint8_t* valid, const uint8_t* 
     const long long hw = (long long)H * W;
     const long long bpf = (hw + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
     if (hw * B >= (1ll << 31) || bpf * B >= (1ll << 31)) return BF_ERR_CAPACITY;
-    const unsigned nb = (unsigned)(bpf * B);
-    hipStream_t st = bf_stream(stream);
-    hipLaunchKernelGGL(k_pack_count, dim3(nb), dim3(CLOUD_BLOCK), 0, st, valid, (int)hw, (int)bpf, block_counts);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, block_counts, (int)nb, (int)bpf, offsets, B);
-    hipLaunchKernelGGL(k_pack_scatter, dim3(nb), dim3(CLOUD_BLOCK), 0, st, xyz, valid, rgb, (int)hw, (int)bpf,
-                       (const int*)block_counts, xyzrgb);
+    compact<PackSel>((unsigned)(bpf * B), block_counts, (int)bpf, offsets, B, bf_stream(stream), xyz, valid, rgb, (int)hw,
+                     (int)bpf, xyzrgb);
     return bf_check_launch();
 }
 
 // ---- voxel hash map -----------------------------------------------------------------------------------------------
-enum { ST_STORED = 0, ST_NONFINITE, ST_OUT_OF_RANGE, ST_DROPPED_FULL, ST_SATURATED, ST_RUNS, ST_N = 8 };
-
-// the slot of `key` (claimed if new), or -1 when neither the key nor an empty slot was found in `cap` probes.
-// Slots never empty again, so a stale read can only show EMPTY where a key now sits, and the compare-and-swap
-// that follows decides; nothing here waits for another lane or wave.
-__device__ __forceinline__ long long cloud_find(unsigned long long* table, unsigned long long mask, unsigned long long key) {
-    unsigned long long s = cloud_hash(key) & mask;
-    for (unsigned long long i = 0; i <= mask; ++i, s = (s + 1) & mask) {
-        unsigned long long* kp = table + s * CLOUD_SLOT_WORDS;
-        unsigned long long k = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == CLOUD_EMPTY) {
-            k = atomicCAS(kp, CLOUD_EMPTY, key);
-            if (k == CLOUD_EMPTY) return (long long)s;
-        }
-        if (k == key) return (long long)s;
-    }
-    return -1;
-}
-
-// per-block counters in LDS: one ballot per wave, one global add per block and non-zero counter at the end
-__device__ __forceinline__ void cloud_stat(unsigned* block_stats, int which, bool flag) {
-    const unsigned long long m = __ballot(flag);
-    if (m && bf_lane() == 0) atomicAdd(block_stats + which, (unsigned)__popcll(m));
-}
-
 // one thread per point; lanes of a wave that hold the same voxel in adjacent lanes form a run, and the run's
 // first lane adds the run's sums (four 64-bit integer adds per run)
 __global__ void __launch_bounds__(CLOUD_BLOCK) k_cloud_integrate(const float* __restrict__ xyz, const uint8_t* __restrict__ valid,
@@ -190,35 +152,32 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_cloud_integrate(const float* __
                                                                  unsigned long long* __restrict__ table,
                                                                  unsigned long long mask, unsigned long long* __restrict__ stats,
                                                                  int merge) {
-    __shared__ unsigned bstats[ST_N];
-    if (threadIdx.x < ST_N) bstats[threadIdx.x] = 0;
-    __syncthreads();
+    __shared__ unsigned bstats[BF_STATS_WORDS];
+    stats_begin(bstats);
     const long long p = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
     const int lane = bf_lane();
     bool live = p < n && valid[p] != 0;
-    unsigned long long key = CLOUD_EMPTY;
+    unsigned long long key = BF_KEY_EMPTY;
     unsigned q01 = 0, q2r = 0, gb = 0;                          // 16-bit pairs: qx | qy, qz | r, g | b
     bool nonfinite = false, out_of_range = false;
     if (live) {
         const float x = xyz[3 * p], y = xyz[3 * p + 1], z = xyz[3 * p + 2];
         const float fx = floorf(x / fine_step), fy = floorf(y / fine_step), fz = floorf(z / fine_step);
-        const float lim = 268435456.0f;                         // 2^28 fine steps = 2^20 voxels
         if (!(isfinite(x) && isfinite(y) && isfinite(z))) {
             nonfinite = true;
-        } else if (!(fx >= -lim && fx < lim && fy >= -lim && fy < lim && fz >= -lim && fz < lim)) {
+        } else if (!key_in_range(fx, fy, fz, (float)BF_KEY_BIAS * BF_CLOUD_FINE_STEPS)) {
             out_of_range = true;
         } else {
             const int ix = (int)fx, iy = (int)fy, iz = (int)fz;
-            key = ((unsigned long long)((ix >> 8) + (1 << 20)) << 42) | ((unsigned long long)((iy >> 8) + (1 << 20)) << 21) |
-                  (unsigned long long)((iz >> 8) + (1 << 20));
+            key = key_pack(ix >> 8, iy >> 8, iz >> 8);
             q01 = (unsigned)(ix & 255) | ((unsigned)(iy & 255) << 16);
             q2r = (unsigned)(iz & 255) | ((unsigned)rgb[3 * p] << 16);
             gb = (unsigned)rgb[3 * p + 1] | ((unsigned)rgb[3 * p + 2] << 16);
         }
     }
-    cloud_stat(bstats, ST_NONFINITE, nonfinite);
-    cloud_stat(bstats, ST_OUT_OF_RANGE, out_of_range);
-    live = key != CLOUD_EMPTY;
+    stat_add(bstats, BF_CLOUD_STAT_NONFINITE, nonfinite);
+    stat_add(bstats, BF_CLOUD_STAT_OUT_OF_RANGE, out_of_range);
+    live = key != BF_KEY_EMPTY;
 
     // runs of equal keys over adjacent lanes (dead lanes carry EMPTY and form runs that are skipped)
     const unsigned long long prev = __shfl_up(key, 1, 64);
@@ -240,18 +199,19 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_cloud_integrate(const float* __
         }
     }
     const bool lead = live && head;
-    cloud_stat(bstats, ST_RUNS, lead);
+    stat_add(bstats, BF_CLOUD_STAT_RUNS, lead);
     const unsigned cnt = (unsigned)(run_end - lane);            // the run's points, in its first lane
 
     long long slot = -1;
     int slow = 0;
     if (lead) {
-        slot = cloud_find(table, mask, key);
+        bool claimed = false;
+        slot = map_find<BF_CLOUD_SLOT_WORDS>(table, mask, key, &claimed);
         if (slot >= 0) {
-            unsigned long long* w = table + slot * CLOUD_SLOT_WORDS;
+            unsigned long long* w = table + slot * BF_CLOUD_SLOT_WORDS;
             const unsigned long long add0 = (unsigned long long)cnt | ((unsigned long long)(s01 & 0xFFFFu) << 32);
             const unsigned long long old = atomicAdd(w + 1, add0);
-            if ((unsigned)(old & 0xFFFFFFFFull) + cnt > CLOUD_MAX_COUNT) {
+            if ((unsigned)(old & 0xFFFFFFFFull) + cnt > BF_CLOUD_MAX_COUNT) {
                 atomicAdd(w + 1, 0ull - add0);                  // over the cap: take the run back, go point by point
                 slow = 1;
             } else {
@@ -266,10 +226,10 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_cloud_integrate(const float* __
     slow = __shfl(slow, leader, 64);
     bool refused = false;
     if (live && slow) {                                         // a voxel at its cap: each point on its own
-        unsigned long long* w = table + slot * CLOUD_SLOT_WORDS;
+        unsigned long long* w = table + slot * BF_CLOUD_SLOT_WORDS;
         const unsigned long long add0 = 1ull | ((unsigned long long)(q01 & 0xFFFFu) << 32);
         const unsigned long long old = atomicAdd(w + 1, add0);
-        if ((unsigned)(old & 0xFFFFFFFFull) >= CLOUD_MAX_COUNT) {
+        if ((unsigned)(old & 0xFFFFFFFFull) >= BF_CLOUD_MAX_COUNT) {
             atomicAdd(w + 1, 0ull - add0);
             refused = true;
         } else {
@@ -278,11 +238,10 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_cloud_integrate(const float* __
             atomicAdd(w + 4, (unsigned long long)(gb >> 16));
         }
     }
-    cloud_stat(bstats, ST_DROPPED_FULL, live && slot < 0);
-    cloud_stat(bstats, ST_SATURATED, refused);
-    cloud_stat(bstats, ST_STORED, live && slot >= 0 && !refused);
-    __syncthreads();
-    if (threadIdx.x < ST_N && bstats[threadIdx.x]) atomicAdd(stats + threadIdx.x, (unsigned long long)bstats[threadIdx.x]);
+    stat_add(bstats, BF_CLOUD_STAT_DROPPED_FULL, live && slot < 0);
+    stat_add(bstats, BF_CLOUD_STAT_SATURATED, refused);
+    stat_add(bstats, BF_CLOUD_STAT_STORED, live && slot >= 0 && !refused);
+    stats_flush(bstats, stats);
 }
 
 BF_API int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint8_t* rgb, long long n, float fine_step,
@@ -300,47 +259,36 @@ BF_API int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint
     return bf_check_launch();
 }
 
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_extract_count(const unsigned long long* __restrict__ table, long long cap,
-                                                               int* __restrict__ counts) {
-    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
-    const bool sel = s < cap && table[s * CLOUD_SLOT_WORDS] != CLOUD_EMPTY;
-    int tot;
-    block_rank(sel, tot);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_extract_scatter(const unsigned long long* __restrict__ table, long long cap,
-                                                                 const int* __restrict__ prefix, long long* __restrict__ key,
-                                                                 unsigned* __restrict__ count, unsigned* __restrict__ sums) {
-    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
-    const unsigned long long* w = table + s * CLOUD_SLOT_WORDS;
-    const bool sel = s < cap && w[0] != CLOUD_EMPTY;
-    int tot;
-    const int r = block_rank(sel, tot);
-    if (!sel) return;
-    const size_t o = (size_t)prefix[blockIdx.x] + r;
-    const unsigned long long a = w[1], b = w[2], c = w[3], d = w[4];
-    key[o] = (long long)w[0];
-    count[o] = (unsigned)a;
-    unsigned* q = sums + o * 6;
-    q[0] = (unsigned)(a >> 32);
-    q[1] = (unsigned)b;
-    q[2] = (unsigned)(b >> 32);
-    q[3] = (unsigned)c;
-    q[4] = (unsigned)(c >> 32);
-    q[5] = (unsigned)d;
-}
+struct CloudSlotSel {                                            // thread t of block b = slot b * CLOUD_BLOCK + t
+    const unsigned long long* table;
+    long long cap;
+    long long* key;
+    unsigned* count;
+    unsigned* sums;
+    __device__ bool selected(unsigned b, unsigned t) const {
+        const long long s = (long long)b * CLOUD_BLOCK + t;
+        return s < cap && table[s * BF_CLOUD_SLOT_WORDS] != BF_KEY_EMPTY;
+    }
+    __device__ void write(unsigned b, unsigned t, size_t row) const {
+        const unsigned long long* w = table + ((long long)b * CLOUD_BLOCK + t) * BF_CLOUD_SLOT_WORDS;
+        const unsigned long long a = w[1], b2 = w[2], c = w[3], d = w[4];
+        key[row] = (long long)w[0];
+        count[row] = (unsigned)a;
+        unsigned* q = sums + row * 6;
+        q[0] = (unsigned)(a >> 32);
+        q[1] = (unsigned)b2;
+        q[2] = (unsigned)(b2 >> 32);
+        q[3] = (unsigned)c;
+        q[4] = (unsigned)(c >> 32);
+        q[5] = (unsigned)d;
+    }
+};
 
 BF_API int bf_cloud_extract(const void* table, long long capacity, int64_t* key, uint32_t* count, uint32_t* sums, int* n_out,
                             int* block_counts, void* stream) {
     if (!table || !key || !count || !sums || !n_out || !block_counts || capacity <= 0) return BF_ERR_ARG;
-    const long long nb = (capacity + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
-    if (capacity >= (1ll << 31) || nb >= (1ll << 31)) return BF_ERR_CAPACITY;
-    hipStream_t st = bf_stream(stream);
-    const unsigned long long* t = (const unsigned long long*)table;
-    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)nb), dim3(CLOUD_BLOCK), 0, st, t, capacity, block_counts);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, block_counts, (int)nb, 0, n_out, 0);
-    hipLaunchKernelGGL(k_extract_scatter, dim3((unsigned)nb), dim3(CLOUD_BLOCK), 0, st, t, capacity,
-                       (const int*)block_counts, (long long*)key, (unsigned*)count, (unsigned*)sums);
+    if (capacity >= (1ll << 31)) return BF_ERR_CAPACITY;
+    compact<CloudSlotSel>(compact_blocks(capacity), block_counts, 0, n_out, 0, bf_stream(stream),
+                          (const unsigned long long*)table, capacity, (long long*)key, (unsigned*)count, (unsigned*)sums);
     return bf_check_launch();
 }

@@ -37,6 +37,13 @@ __device__ __forceinline__ int bf_lanes_below(unsigned long long mask) {
     return __popcll(below);
 }
 
+// every entry of a 4x4 pose is finite (a lost-tracking pose is not)
+__device__ __forceinline__ bool bf_pose_finite(const float* P) {
+    bool finite = true;
+    for (int i = 0; i < 16; ++i) finite = finite && isfinite(P[i]);
+    return finite;
+}
+
 // 4x4 inverse by cofactors in f64, rounded to f32 (rigid poses: exact to ~1 ulp)
 __device__ __forceinline__ void bf_inv4(const float* m32, float* out) {
     double m[16], inv[16];

@@ -18,8 +18,6 @@
 #include "bf_compact.h"
 
 #define FERN_WORD 8                      // ferns per code word: a nibble each
-#define FERN_K_MAX 8
-#define FERN_CELL_MAX 64
 #define FERN_NONE 0x7fffffffffffffffll   // no candidate: above every (distance << 32 | index)
 
 // ---- cell means ------------------------------------------------------------------------------------------------------
@@ -142,7 +140,7 @@ BF_API int bf_fern_table_check(const int32_t* ferns_host, int F, int cells) {
 
 BF_API int bf_fern_encode(const float* depth, const uint8_t* rgb, int B, int H, int W, int cell, float max_depth,
                           const int32_t* ferns, int F, int32_t* means, uint32_t* codes, void* stream) {
-    if (!depth || B <= 0 || H <= 0 || W <= 0 || cell < 1 || cell > FERN_CELL_MAX || !(max_depth > 0.f) ||
+    if (!depth || B <= 0 || H <= 0 || W <= 0 || cell < 1 || cell > BF_FERN_CELL_MAX || !(max_depth > 0.f) ||
         !(max_depth <= 65.535f) || (!means && !codes))
         return BF_ERR_ARG;
     if (codes && (!ferns || F <= 0 || F % FERN_WORD)) return BF_ERR_ARG;
@@ -196,7 +194,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_fern_nearest(const uint32_t* __
                                                               const int* __restrict__ n_dev, int n_upper,
                                                               const uint32_t* __restrict__ queries, int k,
                                                               long long* __restrict__ part, int* __restrict__ rows) {
-    __shared__ long long slot[FERN_K_MAX][CLOUD_WAVES];
+    __shared__ long long slot[BF_FERN_K_MAX][CLOUD_WAVES];
     int n = *n_dev;
     n = n < 0 ? 0 : (n > n_upper ? n_upper : n);
     n = n > capacity ? capacity : n;
@@ -220,7 +218,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_fern_nearest(const uint32_t* __
 // grid Q: the k smallest of a query's blocks * k candidates the same way -> top i32 [Q, k, 2] (distance, index)
 __global__ void __launch_bounds__(CLOUD_BLOCK) k_fern_topk(const long long* __restrict__ part, int candidates, int k,
                                                            int* __restrict__ top) {
-    __shared__ long long slot[FERN_K_MAX][CLOUD_WAVES];
+    __shared__ long long slot[BF_FERN_K_MAX][CLOUD_WAVES];
     const long long* mine = part + (size_t)blockIdx.x * candidates;
     long long prev = -1;
     for (int r = 0; r < k; ++r) {
@@ -243,7 +241,7 @@ BF_API int bf_fern_search_blocks(int n_upper) { return n_upper <= 0 ? 0 : (n_upp
 BF_API int bf_fern_search(const uint32_t* table, int capacity, int F, const int32_t* n, int n_upper, const uint32_t* queries,
                           int Q, int k, long long* part, int32_t* top, int32_t* rows, void* stream) {
     if (!table || !n || !queries || !part || !top || capacity <= 0 || F <= 0 || F % FERN_WORD || n_upper <= 0 ||
-        n_upper > capacity || Q <= 0 || k < 1 || k > FERN_K_MAX)
+        n_upper > capacity || Q <= 0 || k < 1 || k > BF_FERN_K_MAX)
         return BF_ERR_ARG;
     const int blocks = bf_fern_search_blocks(n_upper);
     if (Q > 65535 || (long long)blocks * k >= (1ll << 31) || (long long)Q * n_upper >= (1ll << 31)) return BF_ERR_CAPACITY;
@@ -277,9 +275,9 @@ __global__ void __launch_bounds__(64) k_fern_append(uint32_t* __restrict__ table
         }
     }
     if (threadIdx.x == 0) {
-        counters[0] += 1;                                        // observed
-        if (add && !full) counters[1] += 1;                      // added
-        if (add && full) counters[2] += 1;                       // dropped_full
+        counters[BF_FERN_COUNT_OBSERVED] += 1;
+        if (add && !full) counters[BF_FERN_COUNT_ADDED] += 1;
+        if (add && full) counters[BF_FERN_COUNT_DROPPED_FULL] += 1;
     }
 }
 

@@ -7,7 +7,6 @@
 #include "bf_compact.h"
 
 #define ICP_TERMS 29                     // 21 of J^T J (upper triangle, row by row), 6 of J^T r, sum r^2, inliers
-#define ICP_ROW 32                       // doubles per row of partials / out
 #define ICP_PER_THREAD 4                 // sampled pixels per thread
 #define ICP_PER_BLOCK (CLOUD_BLOCK * ICP_PER_THREAD)
 
@@ -95,14 +94,14 @@ __device__ __forceinline__ double icp_wave_sum(double v) {
 
 // acc (per thread) -> row (32 doubles); every thread of the block must call
 __device__ __forceinline__ void icp_block_sum(double* acc, double* __restrict__ row) {
-    __shared__ double part[CLOUD_WAVES][ICP_ROW];
+    __shared__ double part[CLOUD_WAVES][BF_ICP_ROW];
 #pragma unroll
     for (int i = 0; i < ICP_TERMS; ++i) {
         const double s = icp_wave_sum(acc[i]);
         if (bf_lane() == 0) part[threadIdx.x >> 6][i] = s;
     }
     __syncthreads();
-    if (threadIdx.x < ICP_ROW) {
+    if (threadIdx.x < BF_ICP_ROW) {
         double s = 0.0;
         if (threadIdx.x < ICP_TERMS) {
             s = part[0][threadIdx.x];
@@ -159,7 +158,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_icp_reduce(const float* __restr
         acc[27] += r * r;
         acc[28] += 1.0;
     }
-    icp_block_sum(acc, partials + (size_t)blockIdx.x * ICP_ROW);
+    icp_block_sum(acc, partials + (size_t)blockIdx.x * BF_ICP_ROW);
 }
 
 __global__ void __launch_bounds__(CLOUD_BLOCK) k_icp_final(const double* __restrict__ partials, int blocks,
@@ -168,7 +167,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_icp_final(const double* __restr
 #pragma unroll
     for (int i = 0; i < ICP_TERMS; ++i) acc[i] = 0.0;
     for (int b = threadIdx.x; b < blocks; b += CLOUD_BLOCK) {
-        const double* row = partials + (size_t)b * ICP_ROW;
+        const double* row = partials + (size_t)b * BF_ICP_ROW;
 #pragma unroll
         for (int i = 0; i < ICP_TERMS; ++i) acc[i] += row[i];
     }
@@ -294,7 +293,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_photo_reduce(const float* __res
         acc[27] += r * r;
         acc[28] += 1.0;
     }
-    icp_block_sum(acc, partials + (size_t)blockIdx.x * ICP_ROW);
+    icp_block_sum(acc, partials + (size_t)blockIdx.x * BF_ICP_ROW);
 }
 
 BF_API int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H, int W, int stride, const double* T,

@@ -1,7 +1,7 @@
 // bf_tsdf.hip — the scene mesh: a sparse truncated-signed-distance volume fused from posed depth frames, and a
 // naive-surface-nets extractor over it (the reference leaves mesh.ply to open3d, data_process/README.md:48):
 //   bf_tsdf_touch          the 8x8x8-voxel blocks within the truncation band of every valid depth pixel, claimed in
-//                          an open-addressing hash map (cloud_find's design) and marked with the frame's bit
+//                          an open-addressing hash map (map_find of bf_compact.h) and marked with the frame's bit
 //   bf_tsdf_update         the touched blocks compacted (count / scan / scatter), then one workgroup per block and
 //                          one thread per voxel: every frame whose bit is set is projected into and added
 //   bf_tsdf_extract        the occupied slots, compacted (in slot order)
@@ -9,9 +9,9 @@
 //   bf_tsdf_surface_write  their scans, and the vertices / triangles written at the scanned positions
 //   bf_tsdf_raycast        the volume read back from a pose: one ray per pixel marched through the blocks to the
 //                          surface, as depth / vertex / normal / colour maps (what bf_track.hip aligns a frame to)
-// The volume is three arrays over `capacity` slots: keys u64 (three block indices biased by 2^20, 21 bits each;
-// all ones = empty), touched u64 (bit f = frame f of the launch in flight reaches this block) and vox
-// int32 [capacity, 6, 512]: per voxel (x fastest, then y, then z)
+// The volume is three arrays over `capacity` slots: keys u64 (the key of the block's three indices;
+// BF_KEY_EMPTY = empty), touched u64 (bit f = frame f of the launch in flight reaches this block) and vox
+// int32 [capacity, BF_TSDF_FIELDS, BF_TSDF_VOX]: per voxel (x fastest, then y, then z)
 //   field 0  w      observations          <= max_weight <= 2^20
 //   field 1  sum q  q = rint(min(sdf / trunc, 1) * 1024) in [-1024, 1024], |sum| <= 2^30
 //   field 2  cw     coloured observations <= w
@@ -20,80 +20,32 @@
 // batching, as long as no voxel reached max_weight (such a voxel refuses the observation, counted in `saturated`).
 #include "bf_compact.h"
 
-#define TSDF_EMPTY 0xFFFFFFFFFFFFFFFFull
-#define TSDF_VOX 512
-#define TSDF_FIELDS 6
-#define TSDF_BLOCK_WORDS (TSDF_VOX * TSDF_FIELDS)
-#define TSDF_BIAS (1 << 20)
-#define TSDF_KEY_MASK 0x1FFFFFull
-#define TSDF_MAX_WEIGHT (1 << 20)
+#define TSDF_BLOCK_WORDS (BF_TSDF_VOX * BF_TSDF_FIELDS)
 #define TSDF_UPDATE_GRID 2048
-
-enum { TS_OBSERVATIONS = 0, TS_SKIPPED_POSE, TS_OUT_OF_RANGE, TS_DROPPED_FULL, TS_SATURATED, TS_BLOCKS, TS_N = 8 };
-
-typedef unsigned long long u64;
-
-// the slot of `key` (claimed if new, then *claimed is set), or -1 when neither the key nor an empty slot was
-// found in capacity probes; slots never empty again and nothing here waits for another lane or wave
-__device__ __forceinline__ long long tsdf_find(u64* keys, u64 mask, u64 key, bool* claimed) {
-    u64 s = cloud_hash(key) & mask;
-    for (u64 i = 0; i <= mask; ++i, s = (s + 1) & mask) {
-        u64 k = __hip_atomic_load(keys + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == TSDF_EMPTY) {
-            k = atomicCAS(keys + s, TSDF_EMPTY, key);
-            if (k == TSDF_EMPTY) {
-                *claimed = true;
-                return (long long)s;
-            }
-        }
-        if (k == key) return (long long)s;
-    }
-    return -1;
-}
-
-// the slot of `key` in a table nobody is writing, or -1
-__device__ __forceinline__ int tsdf_lookup(const u64* __restrict__ keys, u64 mask, u64 key) {
-    u64 s = cloud_hash(key) & mask;
-    for (u64 i = 0; i <= mask; ++i, s = (s + 1) & mask) {
-        const u64 k = keys[s];
-        if (k == key) return (int)s;
-        if (k == TSDF_EMPTY) return -1;
-    }
-    return -1;
-}
-
-__device__ __forceinline__ void tsdf_stat(unsigned* block_stats, int which, bool flag) {
-    const u64 m = __ballot(flag);
-    if (m && bf_lane() == 0) atomicAdd(block_stats + which, (unsigned)__popcll(m));
-}
 
 // ---- touch: one thread per depth pixel, blockIdx.x = frame * bpf + the frame's block -------------------------------
 __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_touch(const float* __restrict__ depth, const float* __restrict__ poses,
                                                             int hw, int W, int bpf, float fx, float fy, float cx, float cy,
                                                             float voxel, int T, float max_depth, u64* __restrict__ keys,
                                                             u64* __restrict__ touched, u64 mask, u64* __restrict__ stats) {
-    __shared__ unsigned bstats[TS_N];
+    __shared__ unsigned bstats[BF_STATS_WORDS];
     const int f = blockIdx.x / bpf, j = blockIdx.x - f * bpf;
     const float* P = poses + 16 * f;
-    bool finite = true;
-    for (int i = 0; i < 16; ++i) finite = finite && isfinite(P[i]);
-    if (!finite) {                                               // the whole frame, so the whole block: lost tracking
-        if (j == 0 && threadIdx.x == 0) atomicAdd(stats + TS_SKIPPED_POSE, 1ull);
+    if (!bf_pose_finite(P)) {                                    // the whole frame, so the whole block: lost tracking
+        if (j == 0 && threadIdx.x == 0) atomicAdd(stats + BF_TSDF_STAT_SKIPPED_POSE, 1ull);
         return;
     }
-    if (threadIdx.x < TS_N) bstats[threadIdx.x] = 0;
-    __syncthreads();
+    stats_begin(bstats);
     const int p = j * CLOUD_BLOCK + threadIdx.x;
     const int lane = bf_lane();
     float d = p < hw ? depth[(size_t)f * hw + p] : 0.f;
     const bool live = d > 0.f && d < max_depth;                  // NaN fails
     const float xu = (float)(p % W) - cx, yv = (float)(p / W) - cy;
     const float bs = 8.0f * voxel;
-    const float lim = 1048576.0f;                                // 2^20 blocks
     const u64 bit = 1ull << f;
-    u64 prev_key = TSDF_EMPTY;                                   // the key this thread handled last
+    u64 prev_key = BF_KEY_EMPTY;                                 // the key this thread handled last
     for (int k = -T; k <= T; ++k) {
-        u64 key = TSDF_EMPTY;
+        u64 key = BF_KEY_EMPTY;
         bool out_of_range = false;
         if (live) {
             const float z = d + (float)k * voxel;
@@ -101,38 +53,37 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_touch(const float* __restr
             const float bx = floorf((P[0] * xc + P[1] * yc + P[2] * z + P[3]) / bs);
             const float by = floorf((P[4] * xc + P[5] * yc + P[6] * z + P[7]) / bs);
             const float bz = floorf((P[8] * xc + P[9] * yc + P[10] * z + P[11]) / bs);
-            if (bx >= -lim && bx < lim && by >= -lim && by < lim && bz >= -lim && bz < lim)
-                key = ((u64)((int)bx + TSDF_BIAS) << 42) | ((u64)((int)by + TSDF_BIAS) << 21) | (u64)((int)bz + TSDF_BIAS);
+            if (key_in_range(bx, by, bz))
+                key = key_pack((int)bx, (int)by, (int)bz);
             else
                 out_of_range = true;
         }
-        tsdf_stat(bstats, TS_OUT_OF_RANGE, out_of_range);
+        stat_add(bstats, BF_TSDF_STAT_OUT_OF_RANGE, out_of_range);
         // equal keys merge over this thread's adjacent samples and over adjacent lanes: one probe per run
-        const u64 want = key != prev_key ? key : TSDF_EMPTY;
+        const u64 want = key != prev_key ? key : BF_KEY_EMPTY;
         const u64 left = __shfl_up(want, 1, 64);
-        const bool head = want != TSDF_EMPTY && (lane == 0 || left != want);
+        const bool head = want != BF_KEY_EMPTY && (lane == 0 || left != want);
         bool claimed = false, dropped = false;
         if (head) {
-            const long long slot = tsdf_find(keys, mask, want, &claimed);
+            const long long slot = map_find<1>(keys, mask, want, &claimed);
             if (slot >= 0)
                 atomicOr(touched + slot, bit);
             else
                 dropped = true;
         }
-        tsdf_stat(bstats, TS_BLOCKS, claimed);
-        tsdf_stat(bstats, TS_DROPPED_FULL, dropped);
-        if (key != TSDF_EMPTY) prev_key = key;
+        stat_add(bstats, BF_TSDF_STAT_BLOCKS, claimed);
+        stat_add(bstats, BF_TSDF_STAT_DROPPED_FULL, dropped);
+        if (key != BF_KEY_EMPTY) prev_key = key;
     }
-    __syncthreads();
-    if (threadIdx.x < TS_N && bstats[threadIdx.x]) atomicAdd(stats + threadIdx.x, (u64)bstats[threadIdx.x]);
+    stats_flush(bstats, stats);
 }
 
 BF_API int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, int W, float fx, float fy, float cx,
                          float cy, float voxel, int trunc_voxels, float max_depth, void* keys, void* touched,
                          long long capacity, void* stats, void* stream) {
-    if (!depth || !poses || !keys || !touched || !stats || B <= 0 || B > 64 || H <= 0 || W <= 0 || capacity <= 0 ||
-        (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 || trunc_voxels > 64 || !(max_depth > 0.f) ||
-        !(fx > 0.f) || !(fy > 0.f))
+    if (!depth || !poses || !keys || !touched || !stats || B <= 0 || B > BF_TSDF_MAX_FRAMES || H <= 0 || W <= 0 ||
+        capacity <= 0 || (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 ||
+        trunc_voxels > BF_TSDF_MAX_TRUNC || !(max_depth > 0.f) || !(fx > 0.f) || !(fy > 0.f))
         return BF_ERR_ARG;
     const long long hw = (long long)H * W;
     const long long bpf = (hw + CLOUD_BLOCK - 1) / CLOUD_BLOCK;
@@ -143,49 +94,36 @@ BF_API int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, i
     return bf_check_launch();
 }
 
-// ---- compaction of the slots with a non-zero word (the touched blocks) or a key (the occupied blocks) ------------------
-// key_out == nullptr: select by words[s] != 0; else by words[s] != EMPTY and write the key beside the slot
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_slot_count(const u64* __restrict__ words, long long cap, u64 none,
-                                                                 int* __restrict__ counts) {
-    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
-    const bool sel = s < cap && words[s] != none;
-    int tot;
-    block_rank(sel, tot);
-    if (threadIdx.x == 0) counts[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_slot_scatter(const u64* __restrict__ words, long long cap, u64 none,
-                                                                   const int* __restrict__ prefix, int* __restrict__ slot_out,
-                                                                   long long* __restrict__ key_out) {
-    const long long s = (long long)blockIdx.x * CLOUD_BLOCK + threadIdx.x;
-    const bool sel = s < cap && words[s] != none;
-    int tot;
-    const int r = block_rank(sel, tot);
-    if (!sel) return;
-    const size_t o = (size_t)prefix[blockIdx.x] + r;
-    slot_out[o] = (int)s;
-    if (key_out) key_out[o] = (long long)words[s];
-}
-
-static void tsdf_compact(const u64* words, long long cap, u64 none, int* slot_out, long long* key_out, int* n_out,
-                         int* block_counts, hipStream_t st) {
-    const unsigned nb = (unsigned)((cap + CLOUD_BLOCK - 1) / CLOUD_BLOCK);
-    hipLaunchKernelGGL(k_tsdf_slot_count, dim3(nb), dim3(CLOUD_BLOCK), 0, st, words, cap, none, block_counts);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, block_counts, (int)nb, 0, n_out, 0);
-    hipLaunchKernelGGL(k_tsdf_slot_scatter, dim3(nb), dim3(CLOUD_BLOCK), 0, st, words, cap, none,
-                       (const int*)block_counts, slot_out, key_out);
-}
+// ---- compaction (bf_compact.h) of the slots whose word is not `none`: the touched blocks (touched words, none = 0) or
+// the occupied ones (keys, none = EMPTY; key_out then takes the key beside the slot)
+struct SlotSel {                                                 // thread t of block b = slot b * CLOUD_BLOCK + t
+    const u64* words;
+    long long cap;
+    u64 none;
+    int* slot_out;
+    long long* key_out;
+    __device__ bool selected(unsigned b, unsigned t) const {
+        const long long s = (long long)b * CLOUD_BLOCK + t;
+        return s < cap && words[s] != none;
+    }
+    __device__ void write(unsigned b, unsigned t, size_t row) const {
+        const long long s = (long long)b * CLOUD_BLOCK + t;
+        slot_out[row] = (int)s;
+        if (key_out) key_out[row] = (long long)words[s];
+    }
+};
 
 // ---- update: a workgroup per touched block, a thread per voxel -----------------------------------------------------------
-__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_update(const float* __restrict__ depth, const uint8_t* __restrict__ rgb,
+__global__ void __launch_bounds__(BF_TSDF_VOX) k_tsdf_update(const float* __restrict__ depth,
+                                                          const uint8_t* __restrict__ rgb,
                                                           const float* __restrict__ poses, int B, int H, int W, float fx, float fy,
                                                           float cx, float cy, float voxel, int T, float max_depth,
-                                                          int max_weight, const u64* __restrict__ keys, u64* __restrict__ touched,
+                                                          int max_weight, const u64* __restrict__ keys,
+                                                          u64* __restrict__ touched,
                                                           int* __restrict__ vox, const int* __restrict__ list,
                                                           const int* __restrict__ n_list, u64* __restrict__ stats) {
-    __shared__ unsigned bstats[TS_N];
-    if (threadIdx.x < TS_N) bstats[threadIdx.x] = 0;
-    __syncthreads();
+    __shared__ unsigned bstats[BF_STATS_WORDS];
+    stats_begin(bstats);
     const int t = threadIdx.x;
     const int n = *n_list;
     const float trunc = (float)T * voxel;
@@ -195,13 +133,13 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_update(const float* __restric
         const int slot = list[b];
         const u64 key = keys[slot];
         u64 word = touched[slot] & (B < 64 ? (1ull << B) - 1ull : ~0ull);     // the frames of this launch only
-        const int ix = ((int)((key >> 42) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + (t & 7);
-        const int iy = ((int)((key >> 21) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + ((t >> 3) & 7);
-        const int iz = ((int)(key & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + (t >> 6);
+        const int ix = key_axis(key, 0) * 8 + (t & 7);
+        const int iy = key_axis(key, 1) * 8 + ((t >> 3) & 7);
+        const int iz = key_axis(key, 2) * 8 + (t >> 6);
         const float px = ((float)ix + 0.5f) * voxel, py = ((float)iy + 0.5f) * voxel, pz = ((float)iz + 0.5f) * voxel;
         int* vb = vox + (size_t)slot * TSDF_BLOCK_WORDS + t;
-        int w = vb[0], sq = vb[TSDF_VOX], cw = vb[2 * TSDF_VOX], sr = vb[3 * TSDF_VOX], sg = vb[4 * TSDF_VOX],
-            sb = vb[5 * TSDF_VOX];
+        int w = vb[0], sq = vb[BF_TSDF_VOX], cw = vb[2 * BF_TSDF_VOX], sr = vb[3 * BF_TSDF_VOX], sg = vb[4 * BF_TSDF_VOX],
+            sb = vb[5 * BF_TSDF_VOX];
         while (word) {
             const int f = __ffsll((long long)word) - 1;          // the same in every thread of the workgroup
             word &= word - 1;
@@ -233,39 +171,39 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_update(const float* __restric
             }
         }
         vb[0] = w;
-        vb[TSDF_VOX] = sq;
-        vb[2 * TSDF_VOX] = cw;
-        vb[3 * TSDF_VOX] = sr;
-        vb[4 * TSDF_VOX] = sg;
-        vb[5 * TSDF_VOX] = sb;
+        vb[BF_TSDF_VOX] = sq;
+        vb[2 * BF_TSDF_VOX] = cw;
+        vb[3 * BF_TSDF_VOX] = sr;
+        vb[4 * BF_TSDF_VOX] = sg;
+        vb[5 * BF_TSDF_VOX] = sb;
         __syncthreads();                                         // every thread has read the word
         if (t == 0) touched[slot] = 0;
     }
     n_obs = (unsigned)bf_wave_sum_i32((int)n_obs);
     n_sat = (unsigned)bf_wave_sum_i32((int)n_sat);
     if (bf_lane() == 0) {
-        if (n_obs) atomicAdd(bstats + TS_OBSERVATIONS, n_obs);
-        if (n_sat) atomicAdd(bstats + TS_SATURATED, n_sat);
+        if (n_obs) atomicAdd(bstats + BF_TSDF_STAT_OBSERVATIONS, n_obs);
+        if (n_sat) atomicAdd(bstats + BF_TSDF_STAT_SATURATED, n_sat);
     }
-    __syncthreads();
-    if (threadIdx.x < TS_N && bstats[threadIdx.x]) atomicAdd(stats + threadIdx.x, (u64)bstats[threadIdx.x]);
+    stats_flush(bstats, stats);
 }
 
 BF_API int bf_tsdf_update(const float* depth, const uint8_t* rgb, const float* poses, int B, int H, int W, float fx,
                           float fy, float cx, float cy, float voxel, int trunc_voxels, float max_depth, int max_weight,
                           const void* keys, void* touched, int32_t* vox, long long capacity, int* list, int* n_list,
                           int* block_counts, void* stats, void* stream) {
-    if (!depth || !poses || !keys || !touched || !vox || !list || !n_list || !block_counts || !stats || B <= 0 || B > 64 ||
-        H <= 0 || W <= 0 || capacity <= 0 || (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 ||
-        trunc_voxels > 64 || !(max_depth > 0.f) || max_weight < 1 || max_weight > TSDF_MAX_WEIGHT || !(fx > 0.f) ||
-        !(fy > 0.f))
+    if (!depth || !poses || !keys || !touched || !vox || !list || !n_list || !block_counts || !stats || B <= 0 ||
+        B > BF_TSDF_MAX_FRAMES || H <= 0 || W <= 0 || capacity <= 0 || (capacity & (capacity - 1)) || !(voxel > 0.f) ||
+        trunc_voxels < 1 || trunc_voxels > BF_TSDF_MAX_TRUNC || !(max_depth > 0.f) || max_weight < 1 ||
+        max_weight > BF_TSDF_MAX_WEIGHT || !(fx > 0.f) || !(fy > 0.f))
         return BF_ERR_ARG;
     if (capacity >= (1ll << 31) || (long long)H * W * B >= (1ll << 31)) return BF_ERR_CAPACITY;
     hipStream_t st = bf_stream(stream);
-    tsdf_compact((const u64*)touched, capacity, 0ull, list, nullptr, n_list, block_counts, st);
+    compact<SlotSel>(compact_blocks(capacity), block_counts, 0, n_list, 0, st, (const u64*)touched, capacity, (u64)0, list,
+                     (long long*)nullptr);
     // the list's length is on the device: enough workgroups to fill the machine twice over stride over it
     const unsigned grid = (unsigned)(capacity < TSDF_UPDATE_GRID ? capacity : TSDF_UPDATE_GRID);
-    hipLaunchKernelGGL(k_tsdf_update, dim3(grid), dim3(TSDF_VOX), 0, st, depth, rgb, poses, B, H, W, fx, fy, cx, cy, voxel,
+    hipLaunchKernelGGL(k_tsdf_update, dim3(grid), dim3(BF_TSDF_VOX), 0, st, depth, rgb, poses, B, H, W, fx, fy, cx, cy, voxel,
                        trunc_voxels, max_depth, max_weight, (const u64*)keys, (u64*)touched, (int*)vox, (const int*)list,
                        (const int*)n_list, (u64*)stats);
     return bf_check_launch();
@@ -275,7 +213,8 @@ BF_API int bf_tsdf_extract(const void* keys, long long capacity, int64_t* key, i
                            void* stream) {
     if (!keys || !key || !slot || !n_out || !block_counts || capacity <= 0) return BF_ERR_ARG;
     if (capacity >= (1ll << 31)) return BF_ERR_CAPACITY;
-    tsdf_compact((const u64*)keys, capacity, TSDF_EMPTY, slot, (long long*)key, n_out, block_counts, bf_stream(stream));
+    compact<SlotSel>(compact_blocks(capacity), block_counts, 0, n_out, 0, bf_stream(stream), (const u64*)keys, capacity,
+                     (u64)BF_KEY_EMPTY, slot, (long long*)key);
     return bf_check_launch();
 }
 
@@ -286,20 +225,11 @@ BF_API int bf_tsdf_extract(const void* keys, long long capacity, int64_t* key, i
 #define SURF_EDGE 9
 #define SURF_SAMPLES (SURF_EDGE * SURF_EDGE * SURF_EDGE)
 
-// key of the block at (dx, dy, dz) from `key`, or EMPTY past the index range
-__device__ __forceinline__ u64 tsdf_neighbour_key(u64 key, int dx, int dy, int dz) {
-    const long long x = (long long)((key >> 42) & TSDF_KEY_MASK) + dx, y = (long long)((key >> 21) & TSDF_KEY_MASK) + dy,
-                    z = (long long)(key & TSDF_KEY_MASK) + dz;
-    const long long top = (long long)TSDF_KEY_MASK;
-    if (x < 0 || x > top || y < 0 || y > top || z < 0 || z > top) return TSDF_EMPTY;
-    return ((u64)x << 42) | ((u64)y << 21) | (u64)z;
-}
-
 // WRITE = false: bitmap [n,8] (bit c of word z: cell (c & 7, c >> 3, z) gets a vertex), eflags [n,512] (bits 0-2:
 // the cell's edge from its minimum corner along x / y / z changes sign; bit 3: that corner is inside), vcount [n],
 // rank_of_slot.  WRITE = true: the vertices at vcount (now the exclusive prefix) + the cell's rank.
 template <bool WRITE>
-__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__ keys, u64 mask, const int* __restrict__ vox,
+__global__ void __launch_bounds__(BF_TSDF_VOX) k_tsdf_cells(const u64* __restrict__ keys, u64 mask, const int* __restrict__ vox,
                                                          const long long* __restrict__ skey, const int* __restrict__ sslot,
                                                          int* __restrict__ rank_of_slot, u64* __restrict__ bitmap,
                                                          uint8_t* __restrict__ eflags, int* __restrict__ vcount, float voxel,
@@ -313,13 +243,13 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__
     if (t < 8) {
         int s = sslot[b];
         if (t) {
-            const u64 nk = tsdf_neighbour_key(key, t & 1, (t >> 1) & 1, t >> 2);
-            s = nk == TSDF_EMPTY ? -1 : tsdf_lookup(keys, mask, nk);
+            const u64 nk = key_neighbour(key, t & 1, (t >> 1) & 1, t >> 2);
+            s = nk == BF_KEY_EMPTY ? -1 : map_lookup(keys, mask, nk);
         }
         nslot[t] = s;
     }
     __syncthreads();
-    for (int j = t; j < SURF_SAMPLES; j += TSDF_VOX) {
+    for (int j = t; j < SURF_SAMPLES; j += BF_TSDF_VOX) {
         const int x = j % SURF_EDGE, y = (j / SURF_EDGE) % SURF_EDGE, z = j / (SURF_EDGE * SURF_EDGE);
         const int s = nslot[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
         float val = 0.f;
@@ -328,13 +258,13 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__
             const int* v = vox + (size_t)s * TSDF_BLOCK_WORDS + ((x & 7) | ((y & 7) << 3) | ((z & 7) << 6));
             const int w = v[0];
             if (w > 0) {
-                val = (float)v[TSDF_VOX] / (float)w;
+                val = (float)v[BF_TSDF_VOX] / (float)w;
                 tag = 1u << 25;
-                const int cw = v[2 * TSDF_VOX];
+                const int cw = v[2 * BF_TSDF_VOX];
                 if (cw > 0) {
                     const unsigned h = (unsigned)cw >> 1, c = (unsigned)cw;
-                    tag |= (1u << 24) | (((unsigned)v[3 * TSDF_VOX] + h) / c) | ((((unsigned)v[4 * TSDF_VOX] + h) / c) << 8) |
-                           ((((unsigned)v[5 * TSDF_VOX] + h) / c) << 16);
+                    tag |= (1u << 24) | (((unsigned)v[3 * BF_TSDF_VOX] + h) / c) |
+                           ((((unsigned)v[4 * BF_TSDF_VOX] + h) / c) << 8) | ((((unsigned)v[5 * BF_TSDF_VOX] + h) / c) << 16);
                 }
             }
         }
@@ -366,7 +296,7 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__
         if (active)
             fl = (unsigned)((sv[0] < 0.f) != (sv[1] < 0.f)) | ((unsigned)((sv[0] < 0.f) != (sv[2] < 0.f)) << 1) |
                  ((unsigned)((sv[0] < 0.f) != (sv[4] < 0.f)) << 2) | ((unsigned)(sv[0] < 0.f) << 3);
-        eflags[(size_t)b * TSDF_VOX + t] = (uint8_t)fl;
+        eflags[(size_t)b * BF_TSDF_VOX + t] = (uint8_t)fl;
         if (t == 0) {
             int tot = 0;
             for (int i = 0; i < 8; ++i) tot += wave_n[i];
@@ -396,9 +326,9 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_cells(const u64* __restrict__
         }
     }
     const float cnt = (float)ne;
-    const int ix = ((int)((key >> 42) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + x;
-    const int iy = ((int)((key >> 21) & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + y;
-    const int iz = ((int)(key & TSDF_KEY_MASK) - TSDF_BIAS) * 8 + z;
+    const int ix = key_axis(key, 0) * 8 + x;
+    const int iy = key_axis(key, 1) * 8 + y;
+    const int iz = key_axis(key, 2) * 8 + z;
     float* o = verts + (size_t)rank * 3;
     o[0] = (((float)ix + 0.5f) + sx / cnt) * voxel;
     o[1] = (((float)iy + 0.5f) + sy / cnt) * voxel;
@@ -433,7 +363,8 @@ __device__ __forceinline__ int tsdf_cell_vertex(const u64* __restrict__ bitmap, 
 // a quad per sign-changing edge (from the cell's minimum corner along axis a) whose four cells have a vertex: the
 // cells at 0, -e_b, -e_b-e_c, -e_c with (a, b, c) cyclic run counter-clockwise seen from +a
 template <bool WRITE>
-__global__ void __launch_bounds__(TSDF_VOX) k_tsdf_faces(const u64* __restrict__ keys, u64 mask, const long long* __restrict__ skey,
+__global__ void __launch_bounds__(BF_TSDF_VOX) k_tsdf_faces(const u64* __restrict__ keys, u64 mask,
+                                                         const long long* __restrict__ skey,
                                                          const int* __restrict__ rank_of_slot, const u64* __restrict__ bitmap,
                                                          const uint8_t* __restrict__ eflags, const int* __restrict__ vprefix,
                                                          int* __restrict__ fcount, int* __restrict__ faces) {
@@ -443,14 +374,14 @@ __global__ void __launch_bounds__(TSDF_VOX) k_tsdf_faces(const u64* __restrict__
     if (t < 8) {
         int r = b;
         if (t) {
-            const u64 nk = tsdf_neighbour_key((u64)skey[b], -(t & 1), -((t >> 1) & 1), -(t >> 2));
-            const int s = nk == TSDF_EMPTY ? -1 : tsdf_lookup(keys, mask, nk);
+            const u64 nk = key_neighbour((u64)skey[b], -(t & 1), -((t >> 1) & 1), -(t >> 2));
+            const int s = nk == BF_KEY_EMPTY ? -1 : map_lookup(keys, mask, nk);
             r = s < 0 ? -1 : rank_of_slot[s];
         }
         nrank[t] = r;
     }
     __syncthreads();
-    const unsigned fl = eflags[(size_t)b * TSDF_VOX + t];
+    const unsigned fl = eflags[(size_t)b * BF_TSDF_VOX + t];
     const int xyz[3] = {t & 7, (t >> 3) & 7, t >> 6};
     int quad[3][4];
     int nq = 0;
@@ -519,15 +450,15 @@ BF_API int bf_tsdf_surface_count(const void* keys, long long capacity, const int
                                  int* fprefix, int* totals, void* stream) {
     if (!tsdf_surface_args(keys, capacity, skey, sslot, n, rank_of_slot, bitmap, eflags, vprefix, fprefix) || !vox || !totals)
         return BF_ERR_ARG;
-    if ((long long)n * TSDF_VOX * 3 >= (1ll << 31)) return BF_ERR_CAPACITY;      // vertex and quad indices are int32
+    if ((long long)n * BF_TSDF_VOX * 3 >= (1ll << 31)) return BF_ERR_CAPACITY;      // vertex and quad indices are int32
     hipStream_t st = bf_stream(stream);
     const u64 mask = (u64)(capacity - 1);
     // -1 everywhere: an occupied block that the caller did not list has no vertices for its neighbours
     if (hipMemsetAsync(rank_of_slot, 0xFF, (size_t)capacity * sizeof(int), st) != hipSuccess) return BF_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_tsdf_cells<false>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
+    hipLaunchKernelGGL(k_tsdf_cells<false>, dim3(n), dim3(BF_TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
                        (const long long*)skey, sslot, rank_of_slot, (u64*)bitmap, eflags, vprefix, 0.f, nullptr, nullptr);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, vprefix, n, 0, totals, 0);
-    hipLaunchKernelGGL(k_tsdf_faces<false>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
+    hipLaunchKernelGGL(k_tsdf_faces<false>, dim3(n), dim3(BF_TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
                        (const int*)rank_of_slot, (const u64*)bitmap, (const uint8_t*)eflags, (const int*)vprefix, fprefix,
                        nullptr);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, fprefix, n, 0, totals + 1, 0);
@@ -543,10 +474,10 @@ BF_API int bf_tsdf_surface_write(const void* keys, long long capacity, const int
         return BF_ERR_ARG;
     hipStream_t st = bf_stream(stream);
     const u64 mask = (u64)(capacity - 1);
-    hipLaunchKernelGGL(k_tsdf_cells<true>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
+    hipLaunchKernelGGL(k_tsdf_cells<true>, dim3(n), dim3(BF_TSDF_VOX), 0, st, (const u64*)keys, mask, (const int*)vox,
                        (const long long*)skey, sslot, (int*)rank_of_slot, (u64*)bitmap, (uint8_t*)eflags, (int*)vprefix, voxel,
                        verts, vrgb);
-    hipLaunchKernelGGL(k_tsdf_faces<true>, dim3(n), dim3(TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
+    hipLaunchKernelGGL(k_tsdf_faces<true>, dim3(n), dim3(BF_TSDF_VOX), 0, st, (const u64*)keys, mask, (const long long*)skey,
                        rank_of_slot, (const u64*)bitmap, eflags, vprefix, (int*)fprefix, faces);
     return bf_check_launch();
 }
@@ -571,19 +502,17 @@ BF_API int bf_tsdf_surface_write(const void* keys, long long capacity, const int
 //           A step from a valid inside sample to a valid outside one ends the ray: the camera is behind that surface.
 //   normal  the central differences of s at p_hit +- voxel / 2 along x, y, z, normalised; a pixel with an invalid tap or
 //           a zero gradient is no hit.
-// counters (u64 [8]): hits, rays ended behind a surface, rays that left the range (or ran out of steps), views
-// skipped for a non-finite pose, rays whose hit had no normal.
-enum { RC_HITS = 0, RC_BEHIND, RC_LEFT_RANGE, RC_SKIPPED_POSE, RC_NO_NORMAL };
+// counters (u64 [BF_STATS_WORDS], BF_TSDF_RAY_*): hits, rays ended behind a surface, rays that left the range (or ran
+// out of steps), views skipped for a non-finite pose, rays whose hit had no normal.
 
 // the slot of block (bx, by, bz) as floats (whole numbers), through the lane's one-entry cache; -1: absent or out of range
 __device__ __forceinline__ int rc_block(const u64* __restrict__ keys, u64 mask, float bx, float by, float bz, u64& ckey,
                                         int& cslot) {
-    const float lim = 1048576.0f;
-    if (!(bx >= -lim && bx < lim && by >= -lim && by < lim && bz >= -lim && bz < lim)) return -1;
-    const u64 key = ((u64)((int)bx + TSDF_BIAS) << 42) | ((u64)((int)by + TSDF_BIAS) << 21) | (u64)((int)bz + TSDF_BIAS);
+    if (!key_in_range(bx, by, bz)) return -1;
+    const u64 key = key_pack((int)bx, (int)by, (int)bz);
     if (key != ckey) {
         ckey = key;
-        cslot = tsdf_lookup(keys, mask, key);
+        cslot = map_lookup(keys, mask, key);
     }
     return cslot;
 }
@@ -591,10 +520,10 @@ __device__ __forceinline__ int rc_block(const u64* __restrict__ keys, u64 mask, 
 // the word index of voxel (ix, iy, iz)'s w, or -1
 __device__ __forceinline__ long long rc_voxel(const u64* __restrict__ keys, u64 mask, int ix, int iy, int iz, u64& ckey,
                                               int& cslot) {
-    const u64 key = ((u64)((ix >> 3) + TSDF_BIAS) << 42) | ((u64)((iy >> 3) + TSDF_BIAS) << 21) | (u64)((iz >> 3) + TSDF_BIAS);
+    const u64 key = key_pack(ix >> 3, iy >> 3, iz >> 3);
     if (key != ckey) {
         ckey = key;
-        cslot = tsdf_lookup(keys, mask, key);
+        cslot = map_lookup(keys, mask, key);
     }
     if (cslot < 0) return -1;
     return (long long)cslot * TSDF_BLOCK_WORDS + ((ix & 7) | ((iy & 7) << 3) | ((iz & 7) << 6));
@@ -624,7 +553,7 @@ __device__ __forceinline__ bool rc_sample(const u64* __restrict__ keys, u64 mask
             ok = false;
             continue;
         }
-        v[c] = (float)vox[at + TSDF_VOX] / (float)w / 1024.0f;
+        v[c] = (float)vox[at + BF_TSDF_VOX] / (float)w / 1024.0f;
     }
     if (!ok) return false;
     const float c00 = v[0] + tx * (v[1] - v[0]), c10 = v[2] + tx * (v[3] - v[2]);
@@ -653,14 +582,13 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_raycast(const u64* __restr
     const int u = (tile % tiles_x) * 8 + (lane & 7), v = (tile / tiles_x) * 8 + (lane >> 3);
     const bool in_image = u < W && v < H;
     const float* P = poses + 16 * view;
-    bool finite = true;
-    for (int i = 0; i < 16; ++i) finite = finite && isfinite(P[i]);
+    const bool finite = bf_pose_finite(P);
     const size_t pix = ((size_t)view * H + (in_image ? v : 0)) * W + (in_image ? u : 0);
     float out_d = 0.f, vx = 0.f, vy = 0.f, vz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
     unsigned cr = 0, cg = 0, cb = 0;
     bool hit = false, behind = false, left = false, no_normal = false;
     if (!finite) {
-        if (tile == 0 && lane == 0) atomicAdd(counters + RC_SKIPPED_POSE, 1ull);
+        if (tile == 0 && lane == 0) atomicAdd(counters + BF_TSDF_RAY_SKIPPED_POSE, 1ull);
     } else if (in_image) {
         const float a = ((float)u - cx) / fx, b = ((float)v - cy) / fy;
         const float dx = P[0] * a + P[1] * b + P[2], dy = P[4] * a + P[5] * b + P[6], dz = P[8] * a + P[9] * b + P[10];
@@ -668,7 +596,7 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_raycast(const u64* __restr
         const float len = sqrtf(a * a + b * b + 1.0f);
         const float trunc = (float)T * voxel, bs = 8.0f * voxel;
         const float min_m = 0.25f * voxel;
-        u64 ckey = TSDF_EMPTY;
+        u64 ckey = BF_KEY_EMPTY;
         int cslot = -1;
         float t = near_z, t0 = 0.f, s0 = 0.f;
         bool have = false;                                       // (t0, s0) is a valid sample, the one before this
@@ -738,12 +666,12 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_raycast(const u64* __restr
                     if (qx >= -lim && qx < lim && qy >= -lim && qy < lim && qz >= -lim && qz < lim) {
                         const long long at = rc_voxel(keys, mask, (int)qx, (int)qy, (int)qz, ckey, cslot);
                         if (at >= 0) {
-                            const int cw = vox[at + 2 * TSDF_VOX];
+                            const int cw = vox[at + 2 * BF_TSDF_VOX];
                             if (cw > 0) {
                                 const unsigned hw = (unsigned)cw >> 1, c = (unsigned)cw;
-                                cr = ((unsigned)vox[at + 3 * TSDF_VOX] + hw) / c;
-                                cg = ((unsigned)vox[at + 4 * TSDF_VOX] + hw) / c;
-                                cb = ((unsigned)vox[at + 5 * TSDF_VOX] + hw) / c;
+                                cr = ((unsigned)vox[at + 3 * BF_TSDF_VOX] + hw) / c;
+                                cg = ((unsigned)vox[at + 4 * BF_TSDF_VOX] + hw) / c;
+                                cb = ((unsigned)vox[at + 5 * BF_TSDF_VOX] + hw) / c;
                             }
                         }
                     }
@@ -755,10 +683,10 @@ __global__ void __launch_bounds__(CLOUD_BLOCK) k_tsdf_raycast(const u64* __restr
             }
         }
     }
-    rc_count(counters, RC_HITS, hit);
-    rc_count(counters, RC_BEHIND, behind);
-    rc_count(counters, RC_LEFT_RANGE, left);
-    rc_count(counters, RC_NO_NORMAL, no_normal);
+    rc_count(counters, BF_TSDF_RAY_HITS, hit);
+    rc_count(counters, BF_TSDF_RAY_BEHIND, behind);
+    rc_count(counters, BF_TSDF_RAY_LEFT_RANGE, left);
+    rc_count(counters, BF_TSDF_RAY_NO_NORMAL, no_normal);
     if (!in_image) return;
     depth[pix] = out_d;
     vertex[pix * 3] = vx;
@@ -779,8 +707,9 @@ BF_API int bf_tsdf_raycast(const void* keys, const int32_t* vox, long long capac
                            int min_weight, int max_steps, float* depth, float* vertex, float* normal, uint8_t* rgb,
                            void* counters, void* stream) {
     if (!keys || !vox || !poses || !depth || !vertex || !normal || !counters || V <= 0 || H <= 0 || W <= 0 || capacity <= 0 ||
-        (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 || trunc_voxels > 64 || !(near_z >= 0.f) ||
-        !(far_z > near_z) || !(far_z < INFINITY) || min_weight < 1 || max_steps < 1 || !(fx > 0.f) || !(fy > 0.f))
+        (capacity & (capacity - 1)) || !(voxel > 0.f) || trunc_voxels < 1 || trunc_voxels > BF_TSDF_MAX_TRUNC ||
+        !(near_z >= 0.f) || !(far_z > near_z) || !(far_z < INFINITY) || min_weight < 1 || max_steps < 1 || !(fx > 0.f) ||
+        !(fy > 0.f))
         return BF_ERR_ARG;
     const long long tiles_x = (W + 7) / 8, tiles = tiles_x * ((H + 7) / 8);
     const long long bpv = (tiles + CLOUD_WAVES - 1) / CLOUD_WAVES;

@@ -13,10 +13,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from boxfusion_amd import _lib
+from boxfusion_amd import _abi, _lib
 
-KEY_BIAS = 1 << 20              # voxel indices are stored biased, 21 bits per axis
-KEY_MASK = (1 << 21) - 1
+KEY_BITS = _abi.constants()["BF_KEY_BITS"]          # voxel indices are stored biased, KEY_BITS per axis
+KEY_BIAS, KEY_MASK = _abi.constants()["BF_KEY_BIAS"], (1 << KEY_BITS) - 1
 
 
 def _batched(xyz, valid, rgb_u8):
@@ -91,7 +91,7 @@ class SceneCloud:
         ((index * 256 + mean offset + 0.5) * fine_step, in f64 until the cast) and the rounded mean
         colour of every occupied voxel"""
         key, count, sums = self.raw()
-        idx = torch.stack([(key >> 42) & KEY_MASK, (key >> 21) & KEY_MASK, key & KEY_MASK], 1) - KEY_BIAS
+        idx = torch.stack([(key >> 2 * KEY_BITS) & KEY_MASK, (key >> KEY_BITS) & KEY_MASK, key & KEY_MASK], 1) - KEY_BIAS
         c = count[:, None]
         xyz = ((idx * 256).double() + sums[:, :3].double() / c.double() + 0.5) * float(self.fine_step)
         rgb = (sums[:, 3:] + c // 2) // c

@@ -21,7 +21,7 @@ import torch
 
 from boxfusion_amd import _lib
 
-MAX_FRAMES = 64                 # frames of one launch: the bits of a block's touched word
+MAX_FRAMES = _lib.TSDF_MAX_FRAMES       # frames of one launch: the bits of a block's touched word
 
 
 class TsdfVolume:
@@ -122,7 +122,7 @@ class TsdfVolume:
             raise ValueError("raycast: 0 <= near < far and min_weight >= 1")
         # every step is at least a quarter voxel long: the range in quarter voxels bounds the march
         steps = int(min(max(np.ceil((far - float(near)) / (0.25 * float(self.voxel))) + 16, 16), 1 << 20))
-        counters = torch.zeros(8, dtype=torch.int64, device=self.device)
+        counters = torch.zeros(_lib.STATS_WORDS, dtype=torch.int64, device=self.device)
         d, v, n, c = _lib.tsdf_raycast(self.keys, self.vox, poses, (K[0, 0], K[1, 1], K[0, 2], K[1, 2]), H, W, self.voxel,
                                        self.trunc_voxels, near, far, min_weight, steps, counters, colour=colour)
         return d, v, n, c, counters

@@ -655,6 +655,26 @@ int bf_resize_bicubic_u8(const uint8_t* src, int F, int Hs, int Ws, int Hd, int 
                          const int* bx, int ksx, const int* ky, const int* by, int ksy, uint8_t* tmp,
                          uint8_t* dst, void* stream);
 
+/* A voxel key (the cloud table's voxels, the TSDF volume's blocks): three indices of BF_KEY_BITS bits,
+ * each biased by BF_KEY_BIAS, x << 2 BF_KEY_BITS | y << BF_KEY_BITS | z; BF_KEY_EMPTY marks a free slot. */
+#define BF_KEY_BITS 21
+#define BF_KEY_BIAS (1 << 20)
+#define BF_KEY_EMPTY 0xFFFFFFFFFFFFFFFFull
+/* words of every uint64 `stats` / `counters` tensor below; those past the named indices stay 0 */
+#define BF_STATS_WORDS 8
+
+#define BF_CLOUD_SLOT_WORDS 5           /* uint64 words of a cloud slot */
+#define BF_CLOUD_MAX_COUNT (1u << 24)   /* points a voxel holds before it refuses */
+#define BF_CLOUD_FINE_STEPS 256         /* fine steps per voxel and axis */
+enum {                                  /* indices into bf_cloud_integrate's stats */
+    BF_CLOUD_STAT_STORED = 0,
+    BF_CLOUD_STAT_NONFINITE,
+    BF_CLOUD_STAT_OUT_OF_RANGE,
+    BF_CLOUD_STAT_DROPPED_FULL,
+    BF_CLOUD_STAT_SATURATED,
+    BF_CLOUD_STAT_RUNS
+};
+
 /* entries of the block_counts workspace of bf_cloud_pack (items_per_group = H*W, groups = B) and of
  * bf_cloud_extract (items_per_group = capacity, groups = 1) */
 size_t bf_cloud_blocks(long long items_per_group, int groups);
@@ -668,15 +688,16 @@ int bf_cloud_pack(const float* xyz, const uint8_t* valid, const uint8_t* rgb, in
                   float* xyzrgb, int* offsets, int* block_counts, void* stream);
 
 /* The valid points of n pixels (xyz f32 [n,3], valid u8 [n], rgb u8 [n,3]) into a voxel hash map.
- * Per axis f = floorf(x / fine_step) with fine_step = voxel / 256 (f32), voxel index f >> 8,
- * in-voxel offset f & 255.  table: uint64 [capacity,5], capacity a power of two; a slot is the key
- * (three 21-bit indices biased by 2^20, x << 42 | y << 21 | z; all ones = empty) and eight uint32:
+ * Per axis f = floorf(x / fine_step) with fine_step = voxel / BF_CLOUD_FINE_STEPS (f32), voxel index f >> 8,
+ * in-voxel offset f & 255.  table: uint64 [capacity,BF_CLOUD_SLOT_WORDS], capacity a power of two; a
+ * slot is the key (of the voxel indices; BF_KEY_EMPTY = empty) and eight uint32:
  * count, the three offset sums, the three colour sums, 0.  A new table has every key all ones and
  * everything else zero.  Integer adds only, so the contents do not depend on the order of arrival;
  * merge != 0 sums runs of equal keys over adjacent lanes first (same contents, fewer atomics).
- * stats: uint64 [8], added to: points stored, non-finite (skipped), index outside +-2^20 (skipped),
- * dropped because neither the key nor an empty slot was found in capacity probes, refused by a voxel
- * that holds 2^24 points, runs (sets of atomic adds issued), 0, 0. */
+ * stats: uint64 [BF_STATS_WORDS], added to in the order of BF_CLOUD_STAT_*: points stored, non-finite
+ * (skipped), index outside +-BF_KEY_BIAS (skipped), dropped because neither the key nor an empty slot
+ * was found in capacity probes, refused by a voxel that holds BF_CLOUD_MAX_COUNT points, runs (sets of
+ * atomic adds issued), 0, 0. */
 int bf_cloud_integrate(const float* xyz, const uint8_t* valid, const uint8_t* rgb, long long n,
                        float fine_step, void* table, long long capacity, void* stats, int merge,
                        void* stream);
@@ -691,20 +712,35 @@ int bf_cloud_extract(const void* table, long long capacity, int64_t* key, uint32
  * making it to open3d, data_process/README.md:48; here a TSDF volume on the device and surface nets) ----
  *
  * The volume is three arrays over `capacity` slots (a power of two below 2^31), one slot per block of
- * 8x8x8 voxels: keys uint64 [capacity] (the block's three indices floor(x / (8 * voxel)) biased by
- * 2^20, 21 bits each, x highest; all ones = empty), touched uint64 [capacity] (zero between calls)
- * and vox int32 [capacity,6,512]: for voxel x + 8 y + 64 z of the block the observation count w,
+ * 8x8x8 voxels: keys uint64 [capacity] (the key of the block's three indices floor(x / (8 * voxel));
+ * BF_KEY_EMPTY = empty), touched uint64 [capacity] (zero between calls) and vox int32
+ * [capacity,BF_TSDF_FIELDS,BF_TSDF_VOX]: for voxel x + 8 y + 64 z of the block the observation count w,
  * the sum of q = rint(min(sdf / trunc, 1) * 1024), the coloured-observation count cw, and the sums of
- * r, g, b.  stats: uint64 [8], added to: voxel observations, frames skipped for a non-finite pose,
- * ray samples whose block index lies outside +-2^20, probes that found neither the block nor an empty
- * slot in capacity steps, observations refused by a voxel at max_weight, blocks claimed, 0, 0.
+ * r, g, b.  stats: uint64 [BF_STATS_WORDS], added to in the order of BF_TSDF_STAT_*: voxel
+ * observations, frames skipped for a non-finite pose, ray samples whose block index lies outside
+ * +-BF_KEY_BIAS, probes that found neither the block nor an empty slot in capacity steps, observations
+ * refused by a voxel at max_weight, blocks claimed, 0, 0.
  *
- * bf_tsdf_touch: depth f32 [B,H,W] metres and poses f32 [B,4,4] camera-to-world of B <= 64 frames
+ * bf_tsdf_touch: depth f32 [B,H,W] metres and poses f32 [B,4,4] camera-to-world of B <=
+ * BF_TSDF_MAX_FRAMES frames (trunc_voxels <= BF_TSDF_MAX_TRUNC)
  * with one pinhole (fx, fy, cx, cy; pixel centres at integers).  A pixel is valid when
  * 0 < d < max_depth.  Its ray is sampled at camera depths z = d + k * voxel, k = -trunc_voxels ..
  * trunc_voxels: ((u - cx) * z / fx, (v - cy) * z / fy, z) through the pose, all f32 left to right;
  * the sample's block is claimed and bit b of its touched word set.  A frame whose pose has a
  * non-finite entry is skipped whole. */
+#define BF_TSDF_VOX 512                 /* voxels of a block */
+#define BF_TSDF_FIELDS 6                /* int32 fields of a voxel: w, sum q, cw, sum r, g, b */
+#define BF_TSDF_MAX_WEIGHT (1 << 20)
+#define BF_TSDF_MAX_FRAMES 64           /* frames of one touch / update launch: the bits of a touched word */
+#define BF_TSDF_MAX_TRUNC 64            /* largest trunc_voxels */
+enum {                                  /* indices into the stats of bf_tsdf_touch / bf_tsdf_update */
+    BF_TSDF_STAT_OBSERVATIONS = 0,
+    BF_TSDF_STAT_SKIPPED_POSE,
+    BF_TSDF_STAT_OUT_OF_RANGE,
+    BF_TSDF_STAT_DROPPED_FULL,
+    BF_TSDF_STAT_SATURATED,
+    BF_TSDF_STAT_BLOCKS
+};
 int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, int W, float fx, float fy,
                   float cx, float cy, float voxel, int trunc_voxels, float max_depth, void* keys,
                   void* touched, long long capacity, void* stats, void* stream);
@@ -715,7 +751,7 @@ int bf_tsdf_touch(const float* depth, const float* poses, int B, int H, int W, f
  * pixel (floor(fx x / z + cx + 0.5), floor(fy y / z + cy + 0.5)) inside the image with a valid
  * depth d; sdf = d - z >= -trunc (trunc = trunc_voxels * voxel): w += 1, sum q += q, and if rgb (u8
  * [B,H,W,3], may be null) and sdf <= trunc the colour sums and cw.  A voxel with w == max_weight
- * (<= 2^20) refuses.  The touched words are zero again afterwards. */
+ * (<= BF_TSDF_MAX_WEIGHT) refuses.  The touched words are zero again afterwards. */
 int bf_tsdf_update(const float* depth, const uint8_t* rgb, const float* poses, int B, int H, int W,
                    float fx, float fy, float cx, float cy, float voxel, int trunc_voxels,
                    float max_depth, int max_weight, const void* keys, void* touched, int32_t* vox,
@@ -739,7 +775,7 @@ int bf_tsdf_extract(const void* keys, long long capacity, int64_t* key, int* slo
  * _count fills the scratch (rank_of_slot int32 [capacity]: a listed slot's position in skey, -1 for
  * every other slot -- an occupied block that is not listed still lends its samples to the listed
  * blocks' cells, but has no vertices, and a quad that would need one is left out;
- * bitmap uint64 [n,8], eflags u8 [n,512], vprefix / fprefix int32 [n]) and totals int32 [2] on the
+ * bitmap uint64 [n,8], eflags u8 [n,BF_TSDF_VOX], vprefix / fprefix int32 [n]) and totals int32 [2] on the
  * device: vertices, quads.  _write then
  * writes verts f32 [totals[0],3], vrgb u8 [totals[0],3] and faces int32 [2 * totals[1],3]. */
 int bf_tsdf_surface_count(const void* keys, long long capacity, const int32_t* vox,
@@ -945,10 +981,17 @@ int bf_obb_iou_exact(const double* a, int P, const double* b, int G, double* iou
  * normal f32 [V,H,W,3] (world; the normalised central differences of the field at the hit +- half a
  * voxel, towards the outside; a hit with an invalid tap or a zero gradient is no hit), rgb u8
  * [V,H,W,3] or NULL (the rounded mean colour of the voxel that holds the hit, 128 where it has none,
- * 0 where there is no hit).  counters uint64 [8], added to: hits, rays ended behind a surface, rays
- * that left the range or ran out of steps, views skipped for a non-finite pose (all zero), hits
- * dropped for their normal, 0, 0, 0.  All f32, left to right, no contraction: the same bits as the
+ * 0 where there is no hit).  counters uint64 [BF_STATS_WORDS], added to in the order of BF_TSDF_RAY_*:
+ * hits, rays ended behind a surface, rays that left the range or ran out of steps, views skipped for a
+ * non-finite pose (all zero), hits dropped for their normal, 0, 0, 0.  All f32, left to right, no contraction: the same bits as the
  * numpy restatement in tests/track_ref.py. */
+enum {                                  /* indices into bf_tsdf_raycast's counters */
+    BF_TSDF_RAY_HITS = 0,
+    BF_TSDF_RAY_BEHIND,
+    BF_TSDF_RAY_LEFT_RANGE,
+    BF_TSDF_RAY_SKIPPED_POSE,
+    BF_TSDF_RAY_NO_NORMAL
+};
 int bf_tsdf_raycast(const void* keys, const int32_t* vox, long long capacity, const float* poses,
                     int V, int H, int W, float fx, float fy, float cx, float cy, float voxel,
                     int trunc_voxels, float near_z, float far_z, int min_weight, int max_steps,
@@ -970,10 +1013,11 @@ int bf_depth_vertex_normal(const float* depth, int H, int W, float fx, float fy,
  * with + - * / only: p = T v; q = model_w2c p; the model pixel floor(fx qx / qz + cx + 0.5), floor(fy
  * qy / qz + cy + 0.5); rejected when either normal is 0, qz <= 0, the pixel is off the image,
  * |v_m - p|^2 > dist_max^2 or (R n) . n_m < cos_min; else r = n_m . (v_m - p), J = [p x n_m, n_m].
- * out f64 [32]: the 21 upper-triangle entries of J^T J row by row, the 6 of J^T r, sum r^2, the
- * inlier count, 0, 0, 0.  partials f64 [bf_icp_blocks(H, W, stride), 32] is workspace.  The order of
+ * out f64 [BF_ICP_ROW]: the 21 upper-triangle entries of J^T J row by row, the 6 of J^T r, sum r^2, the
+ * inlier count, 0, 0, 0.  partials f64 [bf_icp_blocks(H, W, stride), BF_ICP_ROW] is workspace.  The order of
  * the additions is fixed (a thread's four samples, a butterfly over the wave, the waves, the blocks
  * the same way) and the grid depends on (H, W, stride) alone: the same bits on every run. */
+#define BF_ICP_ROW 32                   /* doubles per row of partials and of out */
 int bf_icp_blocks(int H, int W, int stride);
 int bf_icp_reduce(const float* live_vertex, const float* live_normal, int H, int W, int stride,
                   const double* T, const float* model_vertex, const float* model_normal, int Hm,
@@ -994,9 +1038,9 @@ int bf_grey_u8(const uint8_t* rgb, int B, int H, int W, float* out, void* stream
  * reference depth D at (floor(w + 0.5), floor(u + 0.5)) is not > 0 or |D - qz| > dist_max, or
  * |r| > intensity_max; c is the bilinear intensity at (u, w), (gx, gy) the derivative of that
  * interpolant, r = I_live - c, h = (gx fx / qz, gy fy / qz, -(gx fx qx + gy fy qy) / qz^2),
- * g = R^T h with R the left 3 x 3 of ref_w2c, J = [p x g, g].  out f64 [32]: the 21 upper-triangle
- * entries of J^T J, the 6 of J^T r, sum r^2, the inlier count, 0, 0, 0.  partials f64
- * [bf_icp_blocks(H, W, stride), 32] is workspace. */
+ * g = R^T h with R the left 3 x 3 of ref_w2c, J = [p x g, g].  out f64 [BF_ICP_ROW]: the 21
+ * upper-triangle entries of J^T J, the 6 of J^T r, sum r^2, the inlier count, 0, 0, 0.  partials f64
+ * [bf_icp_blocks(H, W, stride), BF_ICP_ROW] is workspace. */
 int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H, int W, int stride,
                     const double* T, const float* ref_intensity, const float* ref_depth, int Hr,
                     int Wr, const double* ref_w2c, double fx, double fy, double cx, double cy,
@@ -1004,7 +1048,7 @@ int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H
                     void* stream);
 
 /* ---- relocalisation: randomised ferns over a frame's cell means, a keyframe table of codes ---------
- * A frame is depth f32 [H,W] metres and, optionally, rgb u8 [H,W,3].  With cell size c (1 .. 64) the
+ * A frame is depth f32 [H,W] metres and, optionally, rgb u8 [H,W,3].  With cell size c (1 .. BF_FERN_CELL_MAX) the
  * grid is Hc = H / c by Wc = W / c cells of n = c^2 pixels (the remainder rows and columns are
  * ignored; no cell at all is BF_ERR_ARG).  Colour mean per channel: (2 S + n) / (2 n) of the sum S, in
  * integer division; 0 without an image.  Depth: a pixel is valid when 0 < d < max_depth (NaN fails;
@@ -1021,7 +1065,7 @@ int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H
  * bf_fern_search: the distance of two codes is the number of ferns whose nibbles differ (per word
  * x = a ^ b, popcount of (x | x >> 1 | x >> 2 | x >> 3) & 0x11111111).  table u32 [capacity, F / 8];
  * n i32 [1] on the device, the keyframes held; n_upper (host, n <= n_upper <= capacity) sizes the
- * grid; queries u32 [Q, F / 8]; k <= 8.  top i32 [Q, k, 2]: the k smallest (distance, index) by
+ * grid; queries u32 [Q, F / 8]; k <= BF_FERN_K_MAX.  top i32 [Q, k, 2]: the k smallest (distance, index) by
  * distance, then index, (-1, -1) beyond n.  rows i32 [Q, n_upper] or NULL: every distance, -1 at and
  * beyond n.  part int64 [Q, bf_fern_search_blocks(n_upper), k] is workspace.  Integers only: the same
  * bits on every call.
@@ -1030,7 +1074,11 @@ int bf_photo_reduce(const float* live_vertex, const float* live_intensity, int H
  * this code), the code (u32 [F / 8], device) joins row n of the table when n == 0 or best[0] >
  * threshold (in ferns); pose_host (f32 [16], host, passed by value) goes to row n of poses f32
  * [capacity, 16], frame to ids i32 [capacity], and n becomes n + 1.  A full table changes nothing but
- * the counter.  counters i32 [3], added to: observed, added, dropped_full.  No read-back. */
+ * the counter.  counters i32 [3], added to in the order of BF_FERN_COUNT_*: observed, added,
+ * dropped_full.  No read-back. */
+#define BF_FERN_K_MAX 8
+#define BF_FERN_CELL_MAX 64
+enum { BF_FERN_COUNT_OBSERVED = 0, BF_FERN_COUNT_ADDED, BF_FERN_COUNT_DROPPED_FULL };
 int bf_fern_table_check(const int32_t* ferns_host, int F, int cells);
 int bf_fern_encode(const float* depth, const uint8_t* rgb, int B, int H, int W, int cell,
                    float max_depth, const int32_t* ferns, int F, int32_t* means, uint32_t* codes,

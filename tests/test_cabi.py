@@ -158,3 +158,92 @@ def test_reader_refuses_a_type_it_does_not_know():
 def test_lib_py_assigns_no_signatures_of_its_own():
     from boxfusion_amd import _lib
     assert not re.search(r"\.(restype|argtypes)\b", open(_lib.__file__).read())
+
+
+# ---- the layout constants are written once, in the header (boxfusion_amd/_abi.constants) ----------
+CONSTANTS = {
+    "BF_DEV_OK": 0, "BF_DEV_FUSION_LIST_OVERFLOW": 1, "BF_DEV_HULL_OVERFLOW": 2, "BF_DEV_VIEW_OVERFLOW": 4,
+    "BF_DEV_INDEX_RANGE": 8, "BF_DEV_HULL_TRUNC": 16, "BF_MAX_BOXES": 4096, "BF_ROWS_MAX_FIELDS": 16,
+    "BF_FSEQ_STATE_N": 16,
+    "BF_OK": 0, "BF_ERR_ARG": -1, "BF_ERR_LAUNCH": -2, "BF_ERR_CAPACITY": -3, "BF_ERR_UNSUPPORTED": -4,
+    "BF_KEY_BITS": 21, "BF_KEY_BIAS": 1048576, "BF_KEY_EMPTY": 0xFFFFFFFFFFFFFFFF, "BF_STATS_WORDS": 8,
+    "BF_CLOUD_SLOT_WORDS": 5, "BF_CLOUD_MAX_COUNT": 16777216, "BF_CLOUD_FINE_STEPS": 256,
+    "BF_CLOUD_STAT_STORED": 0, "BF_CLOUD_STAT_NONFINITE": 1, "BF_CLOUD_STAT_OUT_OF_RANGE": 2,
+    "BF_CLOUD_STAT_DROPPED_FULL": 3, "BF_CLOUD_STAT_SATURATED": 4, "BF_CLOUD_STAT_RUNS": 5,
+    "BF_TSDF_VOX": 512, "BF_TSDF_FIELDS": 6, "BF_TSDF_MAX_WEIGHT": 1048576, "BF_TSDF_MAX_FRAMES": 64,
+    "BF_TSDF_MAX_TRUNC": 64,
+    "BF_TSDF_STAT_OBSERVATIONS": 0, "BF_TSDF_STAT_SKIPPED_POSE": 1, "BF_TSDF_STAT_OUT_OF_RANGE": 2,
+    "BF_TSDF_STAT_DROPPED_FULL": 3, "BF_TSDF_STAT_SATURATED": 4, "BF_TSDF_STAT_BLOCKS": 5,
+    "BF_TSDF_RAY_HITS": 0, "BF_TSDF_RAY_BEHIND": 1, "BF_TSDF_RAY_LEFT_RANGE": 2, "BF_TSDF_RAY_SKIPPED_POSE": 3,
+    "BF_TSDF_RAY_NO_NORMAL": 4,
+    "BF_ICP_ROW": 32,
+    "BF_FERN_K_MAX": 8, "BF_FERN_CELL_MAX": 64, "BF_FERN_COUNT_OBSERVED": 0, "BF_FERN_COUNT_ADDED": 1,
+    "BF_FERN_COUNT_DROPPED_FULL": 2,
+    "BF_PNG_BAD_SIGNATURE": 1, "BF_PNG_BAD_HEADER": 2, "BF_PNG_UNSUPPORTED": 4, "BF_PNG_BAD_CHUNK": 8,
+    "BF_PNG_BAD_ZLIB": 16, "BF_PNG_BAD_ADLER": 32, "BF_PNG_BAD_FILTER": 64, "BF_PNG_SIZE": 128,
+    "BF_JPG_BAD_MARKER": 1, "BF_JPG_UNSUPPORTED": 2, "BF_JPG_SIZE": 4, "BF_JPG_BAD_DATA": 8,
+}
+
+
+def test_constants_have_the_written_out_values():
+    from boxfusion_amd import _abi
+    assert _abi.constants() == CONSTANTS
+
+
+def test_lib_py_takes_its_numbers_from_the_header():
+    from boxfusion_amd import _lib, scene_cloud, scene_mesh
+    assert (_lib.BF_DEV_FUSION_LIST_OVERFLOW, _lib.BF_DEV_HULL_OVERFLOW, _lib.BF_DEV_VIEW_OVERFLOW,
+            _lib.BF_DEV_INDEX_RANGE, _lib.BF_DEV_HULL_TRUNC) == (1, 2, 4, 8, 16)
+    assert (_lib.ROWS_MAX_FIELDS, _lib.FSEQ_STATE_N, _lib.STATS_WORDS, _lib.ICP_ROW) == (16, 16, 8, 32)
+    assert (_lib.TSDF_VOX, _lib.TSDF_FIELDS, _lib.TSDF_MAX_WEIGHT, _lib.TSDF_MAX_FRAMES) == (512, 6, 1048576, 64)
+    assert (_lib.CLOUD_SLOT_WORDS, _lib.FERN_K_MAX) == (5, 8)
+    assert sorted(_lib.PNG_STATUS) == [1, 2, 4, 8, 16, 32, 64, 128]
+    assert sorted(_lib.ZLIB_STATUS) == [8, 16, 32, 128] and sorted(_lib.JPEG_STATUS) == [1, 2, 4, 8]
+    assert _lib.PNG_STATUS[64] == "bad row filter" and _lib.JPEG_STATUS[4] == "size mismatch"
+    assert (scene_cloud.KEY_BIAS, scene_cloud.KEY_MASK, scene_mesh.MAX_FRAMES) == (1048576, 2097151, 64)
+
+
+def test_counter_names_follow_the_header_enums():
+    """the tuples _lib.py held as literals before it built them from the enums"""
+    from boxfusion_amd import _lib
+    assert _lib.CLOUD_STATS == ("stored", "nonfinite", "out_of_range", "dropped_full", "saturated", "runs")
+    assert _lib.TSDF_STATS == ("observations", "skipped_pose", "out_of_range", "dropped_full", "saturated", "blocks")
+    assert _lib.TSDF_RAYCAST_STATS == ("hits", "behind", "left_range", "skipped_pose", "no_normal")
+    assert _lib.FERN_COUNTERS == ("observed", "added", "dropped_full")
+
+
+def test_reader_reads_the_literal_forms_and_refuses_the_rest():
+    from boxfusion_amd import _abi
+    text = ("#ifndef BF_GUARD_H\n#define BF_GUARD 7\n#define BF_CALL(x) ((x) + 1)\n#define OTHER 1 + 2\n"
+            "#define BF_A 0x1Full\n#define BF_B (1u << 24)\n#define BF_C ( 3 )\n#define BF_D 12L\n"
+            "typedef enum { BF_E, BF_F = -2, BF_G, BF_H = 1 << 4, BF_I } bf_e;\n")
+    assert _abi.constants(text) == {"BF_GUARD": 7, "BF_A": 31, "BF_B": 1 << 24, "BF_C": 3, "BF_D": 12, "BF_E": 0,
+                                    "BF_F": -2, "BF_G": -1, "BF_H": 16, "BF_I": 17}
+    with pytest.raises(ValueError, match=r"BF_BAD.*'BF_A \* 2'"):
+        _abi.constants("#define BF_BAD BF_A * 2\n")
+    with pytest.raises(ValueError, match=r"BF_OPEN.*'\(1 << 20'"):
+        _abi.constants("#define BF_OPEN (1 << 20\n")
+    with pytest.raises(ValueError, match=r"BF_EMPTY"):
+        _abi.constants("#define BF_EMPTY\n")
+    with pytest.raises(ValueError, match=r"BF_M.*'sizeof\(int\)'"):
+        _abi.constants("enum { BF_L, BF_M = sizeof(int) };\n")
+
+
+def test_python_retypes_no_key_arithmetic():
+    from boxfusion_amd import _lib, scene_cloud, scene_mesh
+    for mod in (_lib, scene_cloud, scene_mesh):
+        # the one `1 << 20` left is scene_mesh.py's cap on a ray's step count: no key, no weight and not in the header
+        src = "\n".join(ln for ln in open(mod.__file__).read().splitlines()
+                        if not (mod is scene_mesh and ln.lstrip().startswith("steps = ")))
+        for literal in ("1 << 20", "<< 42", "0x1FFFFF"):
+            assert literal not in src, (mod.__name__, literal)
+
+
+def test_a_define_cannot_join_a_counter_tuple():
+    from boxfusion_amd import _abi
+    text = "enum { BF_X_STAT_A, BF_X_STAT_B };\n#define BF_X_STAT_LATER 1\nenum { BF_X_RAY_C = 1, BF_X_RAY_D = 0 };\n"
+    assert _abi.enum_names("BF_X_STAT_", text) == ("a", "b") and _abi.enum_names("BF_X_RAY_", text) == ("d", "c")
+    with pytest.raises(KeyError, match="BF_X_NONE_"):
+        _abi.enum_names("BF_X_NONE_", text)
+    with pytest.raises(KeyError, match="2 enums"):
+        _abi.enum_names("BF_X_", text)
