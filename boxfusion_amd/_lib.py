@@ -1792,6 +1792,53 @@ def obb_iou_exact(a, b, with_inter=False):
     return (iou, inter) if with_inter else iou
 
 
+# ------------------------------------------------------------------------------------------
+# objects in the scene (bf_objects.hip; include/boxfusion_objects.h)
+# ------------------------------------------------------------------------------------------
+OBJECTS_HEADER = _abi.EXTENSION_HEADERS[0]
+_OC = _abi.constants(header=OBJECTS_HEADER)
+OBJ_BOX_WORDS, OBJ_COUNT_WORDS, OBJ_EXTENT_WORDS, OBJ_CHUNK = (
+    _OC["BF_OBJ_" + n] for n in ("BOX_WORDS", "COUNT_WORDS", "EXTENT_WORDS", "CHUNK"))
+OBJ_STATS = _abi.enum_names("BF_OBJ_STAT_", header=OBJECTS_HEADER)
+MAX_BOXES = _C["BF_MAX_BOXES"]
+
+
+def _label_points_work(xyz, boxes16, margin=0.0, cull=None):
+    n, b = int(xyz.shape[0]), int(boxes16.shape[0])
+    # 21 f32 operations per point-box test; algorithmic bytes: the points once, a label each, the rows once
+    return dict(kind="label_points", n=n, boxes=b), 21.0 * n * b, 16.0 * n + 4.0 * OBJ_BOX_WORDS * b
+
+
+@_timed(_label_points_work)
+def label_points(xyz, boxes16, margin=0.0, cull=None):
+    """bf_label_points: xyz f32 [n,3], boxes16 f32 [B,16] (centre, three unit axes, half-lengths,
+    volume) -> (labels int32 [n], counts int64 [B,2] = support, owned, extents int32 [B,6] holding the
+    uint32 keys of min / max t_0, t_1, t_2 over the owned points, stats int64 [8] in the order of
+    OBJ_STATS), allocated and initialised here; cull: None (the product's choice) or False / True
+    (bf_label_points_ex, the test and benchmark hook)"""
+    xyz = _need(xyz, torch.float32, "label_points: xyz").contiguous()
+    boxes16 = _need(boxes16, torch.float32, "label_points: boxes16").contiguous()
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or boxes16.dim() != 2 or boxes16.shape[1] != OBJ_BOX_WORDS:
+        raise HipError(f"label_points: xyz [n,3] and boxes16 [B,{OBJ_BOX_WORDS}], got {tuple(xyz.shape)} and "
+                       f"{tuple(boxes16.shape)}")
+    n, b, dev = xyz.shape[0], boxes16.shape[0], xyz.device
+    if boxes16.device != dev:
+        raise HipError("label_points: xyz and boxes16 on one device")
+    if b > MAX_BOXES:
+        raise HipError(f"label_points: {b} boxes, at most {MAX_BOXES} per call")
+    labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros((b, OBJ_COUNT_WORDS), dtype=torch.int64, device=dev)
+    extents = torch.zeros((b, OBJ_EXTENT_WORDS), dtype=torch.int32, device=dev)
+    extents[:, 0::2] = -1                                       # the min words: all ones
+    stats = torch.zeros(STATS_WORDS, dtype=torch.int64, device=dev)
+    args = (_ptr(xyz), n, _ptr(boxes16), b, float(margin), _ptr(labels), _ptr(counts), _ptr(extents), _ptr(stats))
+    if cull is None:
+        _check(lib().bf_label_points(*args, _stream()), "bf_label_points")
+    else:
+        _check(lib().bf_label_points_ex(*args, int(bool(cull)), _stream()), "bf_label_points_ex")
+    return labels, counts, extents, stats
+
+
 FP8 = torch.float8_e4m3fn      # OCP e4m3 (gfx950's fp8; not the MI300 fnuz variant)
 FP8_MAX = 448.0
 _FP8_OUT = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}

@@ -36,6 +36,7 @@ SOURCES = {
     "bf_tsdf.hip": EXACT,
     "bf_track.hip": EXACT,
     "bf_fern.hip": EXACT,
+    "bf_objects.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 
@@ -51,7 +52,8 @@ def _compile(src, flags):
     obj = os.path.join(BUILD, src.replace(".hip", ".o"))
     path = os.path.join(CSRC, src)
     deps = [path, os.path.join(CSRC, "bf_common.h"), os.path.join(CSRC, "bf_cv2.h"), os.path.join(CSRC, "bf_compact.h"),
-            os.path.join(HERE, "..", "include", "boxfusion_hip.h")]
+            os.path.join(HERE, "..", "include", "boxfusion_hip.h"),
+            os.path.join(HERE, "..", "include", "boxfusion_objects.h")]
     if os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in deps
                                    if os.path.exists(d)):
         return obj
