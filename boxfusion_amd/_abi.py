@@ -1,5 +1,5 @@
 """The C types of libboxfusion_hip.so, read from include/boxfusion_hip.h: the one place they are written.
-An extension header (EXTENSION_HEADERS: include/boxfusion_objects.h) is read the same way: every reader
+An extension header (EXTENSION_HEADERS: include/boxfusion_objects.h, include/boxfusion_level.h) is read the same way: every reader
 below takes `header`, the path it reads, and defaults to the core header.
 
 The header is regular: an entry point is `ret bf_name(type name, ...);`, a struct is
@@ -14,7 +14,8 @@ import re
 
 _INCLUDE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include")
 HEADER = os.path.join(_INCLUDE, "boxfusion_hip.h")
-EXTENSION_HEADERS = (os.path.join(_INCLUDE, "boxfusion_objects.h"),)     # each includes the core header
+EXTENSION_HEADERS = (os.path.join(_INCLUDE, "boxfusion_objects.h"),      # each includes the core header
+                     os.path.join(_INCLUDE, "boxfusion_level.h"))
 
 _SCALAR = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
            "long long": ctypes.c_longlong, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}

@@ -1839,7 +1839,137 @@ def label_points(xyz, boxes16, margin=0.0, cull=None):
     return labels, counts, extents, stats
 
 
-FP8 = torch.float8_e4m3fn      # OCP e4m3 (gfx950's fp8; not the MI300 fnuz variant)
+# ------------------------------------------------------------------------------------------
+# levelling a scene (bf_level.hip; include/boxfusion_level.h)
+# ------------------------------------------------------------------------------------------
+LEVEL_HEADER = _abi.EXTENSION_HEADERS[1]
+_LC = _abi.constants(header=LEVEL_HEADER)
+(LEVEL_WEIGHT_CAP, LEVEL_MAX_G, LEVEL_MAX_CANDIDATES, LEVEL_MAX_HEIGHT_BINS, LEVEL_HEIGHT_WORDS, LEVEL_SUM_WORDS,
+ LEVEL_NORMAL_SHIFT, LEVEL_METRE_SHIFT, LEVEL_COORD_LIMIT, LEVEL_STATS_WORDS) = (
+    _LC["BF_LEVEL_" + n] for n in ("WEIGHT_CAP", "MAX_G", "MAX_CANDIDATES", "MAX_HEIGHT_BINS", "HEIGHT_WORDS", "SUM_WORDS",
+                                   "NORMAL_SHIFT", "METRE_SHIFT", "COORD_LIMIT", "STATS_WORDS"))
+LEVEL_STATS = _abi.enum_names("BF_LEVEL_STAT_", header=LEVEL_HEADER)
+
+
+def _level_rows(t, dtype, width, name):
+    t = _need(t, dtype, name).contiguous()
+    if (t.dim() != 2 or t.shape[1] != width) if width else t.dim() != 1:
+        raise HipError(f"{name}: {f'[n,{width}]' if width else '[n]'}, got {tuple(t.shape)}")
+    return t
+
+
+def _level_stats(stats, dev):
+    if stats is None:
+        return torch.zeros(LEVEL_STATS_WORDS, dtype=torch.int64, device=dev)
+    if stats.dtype != torch.int64 or stats.numel() != LEVEL_STATS_WORDS or stats.device != dev:
+        raise HipError(f"stats: int64 [{LEVEL_STATS_WORDS}] on the samples' device")
+    return stats
+
+
+def _level_face_samples_work(vertices, faces, area_unit, stats=None):
+    m = int(faces.shape[0])
+    # two differences, a cross product, a norm and three divisions, a centroid; a face reads 12 + 36 and writes 28 bytes
+    return dict(kind="level_face_samples", faces=m), 40.0 * m, 76.0 * m
+
+
+@_timed(_level_face_samples_work)
+def level_face_samples(vertices, faces, area_unit, stats=None):
+    """bf_level_face_samples: vertices f32 [n,3], faces int32 [m,3] -> (centroids f32 [m,3], unit normals
+    f32 [m,3], weights int32 [m] holding uint32 = the area in units of area_unit, stats int64
+    [LEVEL_STATS_WORDS] in the order of LEVEL_STATS, added to when given)"""
+    vertices = _level_rows(vertices, torch.float32, 3, "level_face_samples: vertices")
+    faces = _level_rows(faces, torch.int32, 3, "level_face_samples: faces")
+    dev = faces.device
+    if vertices.device != dev:
+        raise HipError("level_face_samples: vertices and faces on one device")
+    m = faces.shape[0]
+    centroids = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    weights = torch.empty((m,), dtype=torch.int32, device=dev)
+    stats = _level_stats(stats, dev)
+    _check(lib().bf_level_face_samples(_ptr(vertices), vertices.shape[0], _ptr(faces), m, float(area_unit), _ptr(centroids),
+                                       _ptr(normals), _ptr(weights), _ptr(stats), _stream()), "bf_level_face_samples")
+    return centroids, normals, weights, stats
+
+
+def _level_vote_work(normals, weights, G=32, hist=None, stats=None):
+    n = int(normals.shape[0])
+    return dict(kind="level_vote", n=n, G=int(G)), 12.0 * n, 16.0 * n + 8.0 * 6 * G * G
+
+
+@_timed(_level_vote_work)
+def level_vote(normals, weights, G=32, hist=None, stats=None):
+    """bf_level_vote: normals f32 [n,3], weights int32 [n] (uint32) -> (hist int64 [6 G G], stats), both
+    added to when given"""
+    normals = _level_rows(normals, torch.float32, 3, "level_vote: normals")
+    weights = _level_rows(weights, torch.int32, 0, "level_vote: weights")
+    dev, G = normals.device, int(G)
+    if weights.shape[0] != normals.shape[0] or weights.device != dev:
+        raise HipError("level_vote: one weight per normal, on one device")
+    if not 1 <= G <= LEVEL_MAX_G:
+        raise HipError(f"level_vote: G in 1..{LEVEL_MAX_G}")
+    if hist is None:
+        hist = torch.zeros(6 * G * G, dtype=torch.int64, device=dev)
+    elif hist.dtype != torch.int64 or hist.numel() != 6 * G * G or hist.device != dev:
+        raise HipError(f"level_vote: hist int64 [{6 * G * G}] on the samples' device")
+    stats = _level_stats(stats, dev)
+    _check(lib().bf_level_vote(_ptr(normals), _ptr(weights), normals.shape[0], G, _ptr(hist), _ptr(stats), _stream()),
+           "bf_level_vote")
+    return hist, stats
+
+
+def _level_score_work(hist, G, candidates, cos_par, sin_perp):
+    k = int(candidates.shape[0])
+    return dict(kind="level_score", candidates=k, G=int(G)), 25.0 * k * 6 * G * G, 8.0 * 6 * G * G + 20.0 * k
+
+
+@_timed(_level_score_work)
+def level_score(hist, G, candidates, cos_par, sin_perp):
+    """bf_level_score: hist int64 [6 G G], candidates int32 [k] (bin indices) -> scores int64 [k,2]: the
+    weight parallel (|c.d| >= cos_par) and perpendicular (|c.d| <= sin_perp) to each candidate's centre"""
+    hist = _level_rows(hist, torch.int64, 0, "level_score: hist")
+    candidates = _level_rows(candidates, torch.int32, 0, "level_score: candidates")
+    G, k = int(G), candidates.shape[0]
+    if not 1 <= G <= LEVEL_MAX_G or hist.numel() != 6 * G * G:
+        raise HipError(f"level_score: G in 1..{LEVEL_MAX_G} and hist [6 G G]")
+    if k > LEVEL_MAX_CANDIDATES or candidates.device != hist.device:
+        raise HipError(f"level_score: at most {LEVEL_MAX_CANDIDATES} candidates, on the histogram's device")
+    scores = torch.zeros((k, 2), dtype=torch.int64, device=hist.device)
+    _check(lib().bf_level_score(_ptr(hist), G, _ptr(candidates), k, float(cos_par), float(sin_perp), _ptr(scores),
+                                _stream()), "bf_level_score")
+    return scores
+
+
+def _level_refine_work(points, normals, weights, frame, cos_par, sin_perp, h0=0.0, height_bin=1.0, n_bins=0, stats=None):
+    n = int(points.shape[0])
+    return dict(kind="level_refine", n=n, bins=int(n_bins)), 60.0 * n, 28.0 * n
+
+
+@_timed(_level_refine_work)
+def level_refine(points, normals, weights, frame, cos_par, sin_perp, h0=0.0, height_bin=1.0, n_bins=0, stats=None):
+    """bf_level_refine: points, normals f32 [n,3], weights int32 [n] (uint32), frame f32 [9] = c, e1, e2 ->
+    (sums int64 [LEVEL_SUM_WORDS], heights int64 [n_bins,LEVEL_HEIGHT_WORDS], stats)"""
+    points = _level_rows(points, torch.float32, 3, "level_refine: points")
+    normals = _level_rows(normals, torch.float32, 3, "level_refine: normals")
+    weights = _level_rows(weights, torch.int32, 0, "level_refine: weights")
+    frame = _need(frame, torch.float32, "level_refine: frame").contiguous()
+    dev, n, n_bins = points.device, points.shape[0], int(n_bins)
+    if normals.shape[0] != n or weights.shape[0] != n or frame.numel() != 9:
+        raise HipError("level_refine: one normal and one weight per point, and a frame of 9 floats")
+    if normals.device != dev or weights.device != dev or frame.device != dev:
+        raise HipError("level_refine: every tensor on one device")
+    if not 0 <= n_bins <= LEVEL_MAX_HEIGHT_BINS:
+        raise HipError(f"level_refine: n_bins in 0..{LEVEL_MAX_HEIGHT_BINS}")
+    sums = torch.zeros(LEVEL_SUM_WORDS, dtype=torch.int64, device=dev)
+    heights = torch.zeros((n_bins, LEVEL_HEIGHT_WORDS), dtype=torch.int64, device=dev)
+    stats = _level_stats(stats, dev)
+    _check(lib().bf_level_refine(_ptr(points), _ptr(normals), _ptr(weights), n, _ptr(frame), float(cos_par), float(sin_perp),
+                                 float(h0), float(height_bin), n_bins, _ptr(sums), _ptr(heights) if n_bins else None,
+                                 _ptr(stats), _stream()), "bf_level_refine")
+    return sums, heights, stats
+
+
+FP8 = torch.float8_e4m3fn     # OCP e4m3 (gfx950's fp8; not the MI300 fnuz variant)
 FP8_MAX = 448.0
 _FP8_OUT = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}
 

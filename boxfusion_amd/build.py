@@ -37,6 +37,7 @@ SOURCES = {
     "bf_track.hip": EXACT,
     "bf_fern.hip": EXACT,
     "bf_objects.hip": EXACT,
+    "bf_level.hip": EXACT,
 }
 EXTRA = [s for s in sorted(os.listdir(CSRC)) if s.endswith(".hip") and s not in SOURCES]
 
@@ -53,7 +54,8 @@ def _compile(src, flags):
     path = os.path.join(CSRC, src)
     deps = [path, os.path.join(CSRC, "bf_common.h"), os.path.join(CSRC, "bf_cv2.h"), os.path.join(CSRC, "bf_compact.h"),
             os.path.join(HERE, "..", "include", "boxfusion_hip.h"),
-            os.path.join(HERE, "..", "include", "boxfusion_objects.h")]
+            os.path.join(HERE, "..", "include", "boxfusion_objects.h"),
+            os.path.join(HERE, "..", "include", "boxfusion_level.h")]
     if os.path.exists(obj) and all(os.path.getmtime(obj) >= os.path.getmtime(d) for d in deps
                                    if os.path.exists(d)):
         return obj

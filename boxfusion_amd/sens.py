@@ -9,8 +9,9 @@ bf_jpeg_decode_rgb and the depth streams through bf_zlib_decode_u16 (or PIL / zl
 `python -m boxfusion_amd.sens export scene.sens OUT` writes the tree, `... info scene.sens` prints
 the header, `... cloud scene.sens out.ply` writes the scene's coloured point cloud, `... mesh
 scene.sens out.ply` its surface (a TSDF of the depth frames, scene_mesh.TsdfVolume), `... track scene.sens
-POSES.npy [--recover-lost | --from-scratch] [--photometric] [--relocalise]` poses from tracking the depth frames
-against that TSDF (tracking.track_sequence; for `SensFrameStream(poses=...)`) and `... render
+POSES.npy [--recover-lost | --from-scratch] [--photometric] [--relocalise] [--level]` poses from tracking the depth
+frames against that TSDF (tracking.track_sequence; for `SensFrameStream(poses=...)`; --level turns them into a z-up
+world with the floor at z = 0, scene_level.level_mesh) and `... render
 scene.sens OUT_DIR [--boxes SEQ_boxes.pkl] [--mesh]` orbit and top-down PNG views of the cloud, or with
 --mesh of the TSDF surface (no model needed).
 
@@ -332,7 +333,7 @@ def mesh(sens, voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth
 
 def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=None, step=1, max_depth=10.0,
           capacity=1 << 16, device="cuda", batch=16, photometric=False, relocalise=False, ferns=512, fern_cell=16,
-          harvest=0.15, **tracker_args):
+          harvest=0.15, level=False, **tracker_args):
     """poses for the frames start, start + step, ... below stop by tracking.track_sequence: mode
     "recover-lost" keeps the file's finite poses and tracks the frames written as -inf; "from-scratch"
     starts at the first selected frame's pose (identity if it has none) and tracks every later frame.
@@ -343,19 +344,27 @@ def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=N
     The selected frames are decoded first and held on the device (2.1 MB per 480 x 640 frame): --step /
     --stop bound that for a long capture.
     Returns (poses f32 [num_frames,4,4]: the file's with the selected frames replaced, -inf where a
-    frame stayed lost; the frame indices; info per selected frame; the TsdfVolume)"""
+    frame stayed lost; the frame indices; info per selected frame; the TsdfVolume).
+    level=True levels the tracked volume's surface afterwards (scene_level.level_mesh with the tracked
+    poses) and returns a fifth item, the Levelling.  When it is ok the selected frames' poses are the
+    levelled ones (z up, the floor at z = 0, the walls along x and y) and the volume is a fresh one, the
+    held frames fused again with those poses: a sparse TSDF cannot be rotated in place.  When it is not
+    ok, poses and volume are as without level."""
     import torch
     from boxfusion_amd.scene_mesh import TsdfVolume
     from boxfusion_amd.tracking import Relocaliser, track_sequence
     if mode not in ("recover-lost", "from-scratch"):
         raise ValueError("mode: 'recover-lost' or 'from-scratch'")
-    stream = SensFrameStream(sens, device=device, batch=batch, start=start, stop=stop, step=step)
-    s = stream.sens
+    s = sens if isinstance(sens, SensFile) else SensFile(sens)
+    # a plain RGB-D recording has no pose at all: the stream, used here only to decode the frames, cannot fill them in
+    plain = s.num_frames > 0 and not np.isfinite(s.poses).all((1, 2)).any()
+    stream = SensFrameStream(s, device=device, batch=batch, start=start, stop=stop, step=step,
+                             poses=np.tile(np.eye(4, dtype=np.float32), (s.num_frames, 1, 1)) if plain else None)
     ids = list(stream.frames)
     vol = TsdfVolume(voxel=voxel, trunc_voxels=trunc_voxels, capacity=capacity, max_depth=max_depth, device=device)
     poses = s.poses.copy()
     if not ids:
-        return poses, ids, [], vol
+        return (poses, ids, [], vol, None) if level else (poses, ids, [], vol)
     depths, colours, K = [], [], None
     for sample in stream:
         gt = sample["sensor_info"].gt
@@ -367,10 +376,20 @@ def track(sens, mode="recover-lost", voxel=0.02, trunc_voxels=4, start=0, stop=N
     depths = torch.stack(depths)
     rl = Relocaliser(depths.shape[1], depths.shape[2], device, ferns=ferns, cell=fern_cell, harvest=harvest,
                      max_depth=min(max_depth, 65.535)) if relocalise else None
-    got, infos = track_sequence(depths, K, first_pose=first, known_poses=known, volume=vol, colours=torch.stack(colours),
+    colours = torch.stack(colours)
+    got, infos = track_sequence(depths, K, first_pose=first, known_poses=known, volume=vol, colours=colours,
                                 photometric=photometric, relocaliser=rl, **tracker_args)
     poses[ids] = got
-    return poses, ids, infos, vol
+    if not level:
+        return poses, ids, infos, vol
+    from boxfusion_amd.scene_level import level_mesh
+    levelling = level_mesh(vol, poses=np.asarray(got, np.float32))
+    if levelling.ok:
+        got = levelling.apply(np.asarray(got, np.float32))
+        poses[ids] = got
+        vol = TsdfVolume(voxel=voxel, trunc_voxels=trunc_voxels, capacity=capacity, max_depth=max_depth, device=device)
+        vol.integrate(depths, K, got, colours)
+    return poses, ids, infos, vol, levelling
 
 
 def track_line(file_poses, poses, ids, infos, relocalise=False):
@@ -429,6 +448,9 @@ def parser():
                       help="keep the file's finite poses and track the frames it wrote as -inf (the default)")
     mode.add_argument("--from-scratch", action="store_true", help="ignore the file's poses after the first frame's")
     pt.add_argument("--mesh", help="also write the fused surface as a PLY")
+    pt.add_argument("--level", action="store_true",
+                    help="level the tracked scene (z up, the floor at z = 0, the walls along x and y) and write the poses, "
+                         "and with --mesh the surface fused again from them, in that world")
     pt.add_argument("--photometric", action="store_true",
                     help="track with the colour frames too (an intensity residual against the last placed frame): "
                          "places a textured wall, floor or table top that fills the view")
@@ -496,11 +518,17 @@ def main(argv=None):
             print(vol.stats_line())
         elif a.cmd == "track":
             mode = "from-scratch" if a.from_scratch else "recover-lost"
-            poses, ids, infos, vol = track(s, mode, a.voxel, a.trunc_voxels, a.start, a.stop, a.step, a.max_depth,
-                                           a.capacity, photometric=a.photometric, relocalise=a.relocalise, ferns=a.ferns,
-                                           fern_cell=a.fern_cell, harvest=a.harvest)
+            poses, ids, infos, vol, *levelling = track(s, mode, a.voxel, a.trunc_voxels, a.start, a.stop, a.step,
+                                                       a.max_depth, a.capacity, photometric=a.photometric,
+                                                       relocalise=a.relocalise, ferns=a.ferns, fern_cell=a.fern_cell,
+                                                       harvest=a.harvest, level=a.level)
             np.save(a.poses, poses)
             print(track_line(s.poses, poses, ids, infos, a.relocalise) + f" -> {a.poses}")
+            if a.level and levelling[0] is not None:
+                print(levelling[0].summary())
+                if not levelling[0].ok:
+                    print("warning: this does not look like a room from here; the poses are written unlevelled",
+                          file=sys.stderr)
             if a.mesh:
                 nv, nf = vol.save_ply(a.mesh)
                 print(f"{nv} vertices, {nf} faces -> {a.mesh}")
